@@ -8,8 +8,27 @@ back-solve + x update), run by the Fortran host over the HIP C-ABI exactly as
 a solve does; K timed steps are K consecutive cycles of one solve.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 4096] [--m 95]
-                  [--prec identity|cbpr2|cheb] [--method mgsr|hh] [--no-cpu]
-                  [--plan-only]
+                  [--prec identity|cbpr2|cheb] [--method mgsr|hh]
+                  [--dump-outputs DIR] [--full [--no-cpu] ...] [--plan-only]
+
+A plain run does only what the headline needs: set up, W warmup cycles, the K
+timed cycles (HIP events on the sampled step launches give the line's
+`roofline` entry), and the result line.  --full adds, after the timed region,
+everything else the line can carry: the comparison of the warmup's residual
+history with the reference's own run (`check`), the diagnostic cycle and the
+PCIe-inclusive rate (`diagnostics`), the short legs of the other BASELINE
+configs and the short-recurrence legs (`configs`), and the reference on this
+host's cores (`cpu_baseline`); --no-cpu / --no-diag / --no-configs / --no-sr
+switch single parts of --full off.
+
+--dump-outputs DIR writes what a caller of the timed solve receives from its
+last cycle as float64 DIR/<name>.npy: `x` (the solution, read back after the
+timed region; a fixed seeded sample of 2^20 entries when the grid holds more
+than 2^22 unknowns) and `final_err` (the cycle's m residual estimates): at
+most 32 MiB in all.  The inputs (b = A*1, x0 = 0) depend on the arguments
+alone, so two builds can be compared output for output.  N > 1: the one
+global selection is split by slab, every rank writes its part as
+`x_rank<r>` (their concatenation is the one-GPU `x`), rank 0 `final_err`.
 
 --gpus N > 1: one rank per GPU.  Launched under torch.distributed.run (the
 driver's way) the ranks read RANK/LOCAL_RANK/WORLD_SIZE; launched directly
@@ -1012,6 +1031,34 @@ def kfd_sched_info() -> dict:
     return out
 
 
+DUMP_FULL_MAX = 1 << 22  # unknowns of a grid written whole (32 MiB as float64, over all ranks)
+DUMP_SAMPLE = 1 << 20  # entries of the seeded sample of a larger grid (8 MiB, over all ranks)
+
+
+def dump_sample_index(n: int) -> np.ndarray:
+    """The entries of the GLOBAL n-vector that --dump-outputs keeps: all of them up
+    to DUMP_FULL_MAX, else DUMP_SAMPLE indices drawn with a fixed seed (sorted; the
+    same for every run, build and rank count)."""
+    if n <= DUMP_FULL_MAX:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(20240607).integers(0, n, size=DUMP_SAMPLE))
+
+
+def dump_outputs(d: str, x: np.ndarray, final_err: np.ndarray, rank: int, world: int, n_global: int | None = None,
+                 offset: int = 0) -> None:
+    """--dump-outputs: the kept entries (dump_sample_index of the global vector) that
+    fall into this rank's slab x = x_global[offset : offset + x.size] and, on rank 0,
+    the last cycle's final_err, as float64 .npy files in d.  The budget is the run's,
+    not the rank's: the ranks' files together hold the one global selection."""
+    os.makedirs(d, exist_ok=True)
+    idx = dump_sample_index(x.size if n_global is None else n_global)
+    idx = idx[(idx >= offset) & (idx < offset + x.size)] - offset
+    name = "x" if world == 1 else f"x_rank{rank}"
+    np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(x[idx], dtype=np.float64))
+    if rank == 0:
+        np.save(os.path.join(d, "final_err.npy"), np.ascontiguousarray(final_err, dtype=np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1022,7 +1069,13 @@ def main() -> None:
     ap.add_argument("--prec", default="identity", choices=["identity", "cbpr2", "cheb"])
     ap.add_argument("--degree", type=int, default=8)
     ap.add_argument("--method", default="mgsr", choices=["mgsr", "hh"])
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run everything else the line can carry: the check against "
+                         "the reference's residual history, the diagnostic cycle, the other configs' legs, the "
+                         "short-recurrence legs and the CPU baseline (a plain run does the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed cycle's solve returns (x, final_err) as float64 DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-cap", type=float, default=45.0,
                     help="seconds: the share's leg also runs one full cycle (a check of the fit) if the fit says it "
                          "finishes within this")
@@ -1050,6 +1103,8 @@ def main() -> None:
         print(json.dumps({"sr_legs": sr_legs(ga, with_cpu=not args.no_cpu, tune=args.tune), "tune": args.tune}),
               flush=True)
         return
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu = args.no_configs = args.no_sr = args.no_diag = True
     maybe_self_launch(args, sys.argv[1:])
 
     # No torch in this process: the library runs on the HIP runtime and RCCL it
@@ -1138,8 +1193,8 @@ def main() -> None:
     def guarded_warmup() -> tuple[bool, str]:
         ok, why = 1, ""
         try:
-            if args.warmup > 0:  # from x0 = 0: its cycle 1 is checked against the reference below
-                warm["res"] = run(args.warmup, hist=True)
+            if args.warmup > 0:  # from x0 = 0; --full: its history is checked against the reference below
+                warm["res"] = run(args.warmup, hist=args.full, want_x=args.full)
         except Exception as e:  # noqa: BLE001 - every rank reports, then all agree below
             why = str(e)
             print(f"rank {rank}: warmup failed: {e}", file=sys.stderr)
@@ -1183,9 +1238,12 @@ def main() -> None:
     cycles = res.n_cycles
     iters = (cycles - 1) * m + res.n_out if cycles > 0 else 0
     plan = ctx.res_info(hh=args.method == "hh")  # the resident variant the timed launches ran
+    if args.dump_outputs:  # before any later leg runs more cycles on this context
+        dump_outputs(args.dump_outputs, ctx.get_x(), res.final_err, rank, world, N * N, line0 * N)
+        log(f"outputs written to {args.dump_outputs}")
     diag = None if args.no_diag else diagnostics(ctx, args, run, ctl, world)
-    log("diagnostics done")
     if diag is not None:
+        log("diagnostics done")
         diag["pcie_inclusive"] = pcie_inclusive(ctx, args, run, ctl, line0, nlines)
         if (world > 1 and args.method == "mgsr" and fallback is None
                 and not any(kv.split("=")[0] == "23" for kv in args.tune)):
@@ -1217,7 +1275,7 @@ def main() -> None:
             log("CPU baseline (the reference on this host)")
             cpu = cpu_baseline(N, m, args.prec, args.degree, args.method, args.cpu_cap, args.cpu_steps)
         check = {"true_rel_residual_after_timed_cycles": resid}
-        if "res" in warm and len(warm["res"].hist_res) > 0:
+        if args.full and "res" in warm and len(warm["res"].hist_res) > 0:
             check.update(history_vs_golden(warm["res"].hist_res, *GOLDEN_OF.get((N, m, args.prec, args.method),
                                                                                 (None, None))))
         prec_name = {"identity": "no precond", "cbpr2": "cbpr2", "cheb": f"Chebyshev({args.degree})"}[args.prec]

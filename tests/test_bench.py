@@ -442,6 +442,81 @@ def test_read_scale_finds_bench_lines_in_a_driver_file():
     assert row["verdict"] == "inside band" and row["blocked_S"] == 2 and row["blocked_verdict"] == "below band"
 
 
+def test_dump_outputs_writes_a_fixed_sample(tmp_path):
+    """--dump-outputs: a grid up to 2^22 unknowns is written whole, a larger one as the
+    same seeded sample every time; float64 .npy files, under 64 MB over all ranks."""
+    x = np.arange(1000, dtype=np.float64)
+    fe = np.linspace(1.0, 0.1, 20)
+    d = tmp_path / "out" / "nested"
+    bench.dump_outputs(str(d), x, fe, 0, 1)
+    assert sorted(os.listdir(d)) == ["final_err.npy", "x.npy"]
+    assert np.array_equal(np.load(d / "x.npy"), x) and np.array_equal(np.load(d / "final_err.npy"), fe)
+    assert np.load(d / "x.npy").dtype == np.float64
+    bench.dump_outputs(str(d), x, fe, 1, 2)  # a rank other than 0: its slab only
+    assert sorted(os.listdir(d)) == ["final_err.npy", "x.npy", "x_rank1.npy"]
+    n = 4096 * 4096
+    idx = bench.dump_sample_index(n)
+    assert idx.size == bench.DUMP_SAMPLE and idx.min() >= 0 and idx.max() < n and np.all(np.diff(idx) >= 0)
+    assert np.array_equal(idx, bench.dump_sample_index(n))
+    assert np.array_equal(bench.dump_sample_index(bench.DUMP_FULL_MAX), np.arange(bench.DUMP_FULL_MAX))
+    # the budget is the run's: over the ranks of every split of the default grid (and of one
+    # written whole) the files hold the one global selection, split by slab, under 64 MB
+    import gmres_amd as ga
+
+    for N in (4096, 2048):
+        xg = np.random.default_rng(1).standard_normal(N * N)
+        whole = None
+        for w in (1, 2, 4, 8):
+            dw = tmp_path / f"g{N}_{w}"
+            for r, (l0, nl) in enumerate(ga.slab_partition(N, w)):
+                bench.dump_outputs(str(dw), xg[l0 * N:(l0 + nl) * N], np.ones(95), r, w, N * N, l0 * N)
+            files = sorted(os.listdir(dw))
+            assert files == ["final_err.npy"] + (["x.npy"] if w == 1 else [f"x_rank{r}.npy" for r in range(w)])
+            assert sum(os.path.getsize(dw / f) for f in files) < 64e6, (N, w)
+            got = np.concatenate([np.load(dw / f) for f in files[1:]])
+            whole = got if w == 1 else whole
+            assert np.array_equal(got, whole) and np.array_equal(got, xg[bench.dump_sample_index(N * N)])
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_only(tmp_path):
+    """A plain run: --steps sets the timed cycles, ms_per_step is one cycle's time, nothing
+    beside the headline runs, and --dump-outputs writes the last cycle's x and final_err --
+    equal from run to run, and equal to a solve of as many cycles made directly."""
+    import gmres_amd as ga
+
+    N, m, K = 96, 20, 3
+    lines, outs = [], []
+    for k in range(2):
+        d = tmp_path / f"o{k}"
+        t0 = time.perf_counter()
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K),
+                            "--warmup", "1", "--grid", str(N), "--m", str(m), "--dump-outputs", str(d)],
+                           capture_output=True, text=True, env=_env(), cwd=ROOT, timeout=120)
+        wall = time.perf_counter() - t0
+        assert p.returncode == 0, p.stderr[-3000:]
+        (line,) = [json.loads(x) for x in p.stdout.splitlines() if x.startswith("{")]
+        print(f"run {k}: wall {wall:.2f} s, ms_per_step {line['ms_per_step']}, value {line['value']}")
+        lines.append(line)
+        outs.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    line = lines[0]
+    assert line["steps"] == K and line["config"]["arnoldi_iters"] == K * m
+    assert line["metric"] == bench.METRIC and line["unit"] == "Arnoldi it/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True
+    assert line["value"] == pytest.approx(m / (line["ms_per_step"] * 1e-3), rel=1e-3)
+    assert line["cpu_baseline"] is None and line["diagnostics"] is None and line["configs"] is None
+    assert "pass" not in line["check"]
+    assert sorted(outs[0]) == ["final_err.npy", "x.npy"]
+    for f, a in outs[0].items():
+        assert a.dtype == np.float64 and np.array_equal(a, outs[1][f]), f
+    with ga.Context(N, m) as c:
+        c.set_precond("identity", (8.2, 0.2), 8)
+        c.set_rhs_ones()
+        r = ga.gmres_mgsr(c, 1e-15, max_cycles=K, want_verr=False)
+    assert outs[0]["x.npy"].shape == (N * N,) and outs[0]["final_err.npy"].shape == (m,)
+    assert np.array_equal(outs[0]["x.npy"], r.x) and np.array_equal(outs[0]["final_err.npy"], r.final_err)
+
+
 def test_sr_pmc_traffic_lookup():
     """The short-recurrence legs' dominant pass carries the committed PMC bytes
     (profiles/r06/pmc_sr_traffic_r06as.json): fetch x 2 + write per unknown, the

@@ -379,7 +379,7 @@ def test_bench_two_ranks_default_collective_on_one_gpu():
     env = dict(os.environ, GK_BENCH_SAME_DEVICE="1")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--grid", "1024",
-                        "--steps", "1", "--warmup", "1", "--no-cpu", "--no-diag"],
+                        "--steps", "1", "--warmup", "1", "--full", "--no-cpu", "--no-diag"],
                        capture_output=True, text=True, env=env, cwd=root, timeout=100)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([x for x in p.stdout.splitlines() if x.startswith("{")][-1])

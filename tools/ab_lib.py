@@ -35,7 +35,7 @@ def main() -> None:
                     tune += ["--tune", kv]
             elif v != "base":
                 env["GK_LIB_DIR"] = os.path.join(ROOT, "gmres_amd", "lib", "variants", v)
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", *tune, *extra],
+            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu", *tune, *extra],
                                capture_output=True, text=True, env=env, timeout=a.timeout)
             if p.returncode != 0:
                 print(json.dumps({"variant": v, "round": r, "rc": p.returncode, "err": p.stderr[-800:]}), flush=True)
