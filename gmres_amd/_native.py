@@ -41,6 +41,7 @@ GK_TUNE_RES_BLOCK = 23
 GK_TUNE_WATCHDOG_MS = 24
 GK_TUNE_HH_NORM_ORDER = 25
 GK_TUNE_RES_PF = 27
+GK_TUNE_RES_PIPE = 30
 GK_PREC_IDENTITY, GK_PREC_CBPR2, GK_PREC_CHEB = 0, 1, 2
 (GK_KID_PROJ, GK_KID_STENCIL, GK_KID_SCALE, GK_KID_UPDATE, GK_KID_COMM, GK_KID_OTHER, GK_KID_RES, GK_KID_PREC,
  GK_KID_HALO, GK_KID_GRAPH) = range(10)
@@ -53,7 +54,7 @@ GK_SR_PCG, GK_SR_BICGSTAB = 0, 1
 COMM_KINDS = {0: None, 1: "rccl", 2: "local-group", 3: "xgmi-device-exchange"}
 # resident-step variants (gk_res_info / gk_res_plan_query)
 RES_VARIANTS = {0: None, 1: "prefetch", 2: "pairs", 3: "pairs+lds", 4: "w-only", 5: "w+column", 6: "blocked"}
-RES_INFO_KEYS = ["variant", "G", "r2", "l2", "pf", "cw", "wo", "nt", "r2e", "l2e", "lds", "nres2", "unused12", "cheb_sten", "wt", "blk"]
+RES_INFO_KEYS = ["variant", "G", "r2", "l2", "pf", "cw", "wo", "nt", "r2e", "l2e", "lds", "nres2", "pipe", "cheb_sten", "wt", "blk"]
 
 c_int, c_double, c_ll, c_vp = ctypes.c_int, ctypes.c_double, ctypes.c_longlong, ctypes.c_void_p
 _dp = ctypes.POINTER(ctypes.c_double)

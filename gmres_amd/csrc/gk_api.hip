@@ -148,6 +148,7 @@ struct gk_ctx {
     int tune_res = -1;                              // -1 auto, 0 off, 1 on where possible
     int tune_res_r2 = 0;                            // cap of resident double2 per thread (0 = auto)
     int tune_res_lds = 1;                           // LDS-resident part of w for large slabs
+    int tune_res_pipe = -1;                         // w-only MGS step: pipelined pass (-1: the build's default)
     int tune_res_wonly = -1;                        // large slabs: w-only variant (-1: by the byte model)
     int tune_verr_order = 1;                        // v_err diagnostics in the reference's dot order
     int tune_hh_fuse = 1;                           // Householder step: small launches folded into the chains
@@ -755,6 +756,21 @@ constexpr int RES_RW = GK_RES_RW, RES_LW = GK_RES_LW, RES_LW_HH = 38;
 // Householder 41.05 -> 40.57 us per reflection, while the MGS-R step keeps 88 / 8 (41.2 vs
 // 41.67 us with 90 / 6).
 constexpr int RES_RW_HH = GK_RES_RW_HH;
+#ifndef GK_RES_PIPE
+#define GK_RES_PIPE 1
+#endif
+// The w-only MGS step's software-pipelined pass (k_mgs_wres<.., PIPE = true>: the column
+// loads of half-batch b + 1 in flight while half-batch b is consumed, counted waits), the
+// default of GK_TUNE_RES_PIPE.  It runs only where every workgroup holds exactly RES_RW +
+// RES_LW chunks and nothing is streamed (4096^2 on 256 CUs); every other plan runs the
+// batch-by-batch pass.  A/B at 4096^2, parent build and this one interleaved on one box, three
+// runs each (profiles/r07/ab_pipe_touch_r07.jsonl): 251.5 / 251.8 / 251.9 -> 261.8 / 262.0 /
+// 261.8 it/s, pass 32.65 -> 31.16 us and wait 7.53 -> 7.23 us per projection (with the touch
+// depth of these launches re-tuned 28 -> 20; at 28: 250.9-252.1 -> 257.0-257.5 it/s); the
+// same build with GK_TUNE_RES_PIPE 0: 251.8.  Results bit-identical to the batch pass.
+constexpr bool RES_PIPE = GK_RES_PIPE != 0;
+// (what the pipelined pass asserts: its wait counts within vmcnt's 6 bits, V_q default policy)
+constexpr bool RES_PIPE_OK = 2 * (gk::PIPE_D - 1) <= 63 && RES_RW + RES_LW > gk::PIPE_D && !gk::RES_QNT;
 
 struct ResPlan {
     int G = 0, r2 = 0, l2 = 0;
@@ -766,6 +782,7 @@ struct ResPlan {
                            // 1 with bvar >= 0: the strict step on k_mgs_blk<S = 1> (GK_TUNE_RES_PF)
     int bvar = -1;         // ... its instantiation (gk::BLK_*)
     int wt = 0;            // threads per workgroup = double2 per chunk (set by plan_resident)
+    bool pipe = false;     // w-only MGS step: the software-pipelined pass (full workgroups only)
     i64 nres2 = 0;
     int lds = 0;
 };
@@ -858,7 +875,7 @@ bool wonly_pays(i64 n2, int G) { return wonly_bytes(n2, G) < pairs_bytes(n2, G);
 //   else w and the running column in 2 x 12 registers, plus (GK_TUNE_RES_LDS)
 //   w of 18 more chunks per workgroup in LDS, the rest streamed.
 void plan_resident(i64 nloc, int gmax, int cap, int tune_lds, int tune_wonly, bool hh, bool nt, ResPlan &p,
-                   int tune_pc = -1, int tune_blk = 1, int tune_pf = 0) {
+                   int tune_pc = -1, int tune_blk = 1, int tune_pf = 0, int tune_pipe = -1) {
     const i64 n2 = nloc / 2;
     const i64 dcw = gk::RT - 64;
     // small vectors: no more workgroups than two chunks each (a cheaper all-gather)
@@ -941,6 +958,10 @@ void plan_resident(i64 nloc, int gmax, int cap, int tune_lds, int tune_wonly, bo
         spread(gk::WT, hh ? RES_RW_HH : RES_RW, hh ? RES_LW_HH : RES_LW);
         p.lds = (hh ? RES_LW_HH : RES_LW) * gk::WT * (int)sizeof(double2);
         p.nt = true;  // V_i non-temporal, V_q default policy (fixed in the kernel)
+        // The pipelined pass counts its loads: only where every workgroup holds exactly
+        // RES_RW + RES_LW whole chunks, nothing is streamed and there is no odd element.
+        p.pipe = RES_PIPE_OK && !hh && (tune_pipe < 0 ? RES_PIPE : tune_pipe != 0) && p.r2e == RES_RW &&
+                 p.l2e == RES_LW && nloc % 2 == 0 && n2 == (i64)p.G * (RES_RW + RES_LW) * gk::WT && p.nres2 == n2;
         return;
     } else {
         p.G = gmax;
@@ -972,13 +993,14 @@ bool res_plan(gk_ctx *c, ResPlan &p, bool hh = false) {
     const int gmax = std::max(1, std::min(gk::RGMAX, c->res_cus / std::max(1, c->res_share)));
     const int cap = c->tune_res_r2 > 0 ? c->tune_res_r2 : RES_R2_BIG;
     plan_resident(c->nloc, gmax, cap, c->tune_res_lds, c->tune_res_wonly, hh,
-                  c->tune_nt > 0 || (c->tune_nt < 0 && c->nt_auto), p, c->tune_res_pc, c->tune_res_blk, c->tune_res_pf);
+                  c->tune_nt > 0 || (c->tune_nt < 0 && c->nt_auto), p, c->tune_res_pc, c->tune_res_blk, c->tune_res_pf,
+                  c->tune_res_pipe);
     if (p.wo && !hh && c->m + 1 > gk::WO_HMAX) return false;  // its H column: WO_HMAX entries of LDS
     return true;
 }
 
 // gk_res_plan_query / gk_res_info layout
-enum { RPI_VARIANT = 0, RPI_G, RPI_R2, RPI_L2, RPI_PF, RPI_CW, RPI_WO, RPI_NT, RPI_R2E, RPI_L2E, RPI_LDS, RPI_NRES2, RPI_UNUSED12,
+enum { RPI_VARIANT = 0, RPI_G, RPI_R2, RPI_L2, RPI_PF, RPI_CW, RPI_WO, RPI_NT, RPI_R2E, RPI_L2E, RPI_LDS, RPI_NRES2, RPI_PIPE,
        RPI_CHEB_STEN, RPI_WT, RPI_BLK };
 void plan_info(const ResPlan &p, bool on, long long *info) {
     for (int k = 0; k < GK_RES_INFO_LEN; ++k) info[k] = 0;
@@ -1000,6 +1022,7 @@ void plan_info(const ResPlan &p, bool on, long long *info) {
     info[RPI_LDS] = p.lds;
     info[RPI_NRES2] = p.nres2;
     info[RPI_WT] = p.wt;
+    info[RPI_PIPE] = p.pipe;
 }
 
 // hipFuncSetAttribute is per device: remember the dynamic-LDS size set on each.
@@ -1028,19 +1051,19 @@ int launch_res_t(gk_ctx *c, const ResPlan &p, const gk::ResArgs &a) {
     }
 }
 
-template <int MODE>
+template <int MODE, bool PIPE = false>
 int launch_wres_m(gk_ctx *c, const ResPlan &p, const gk::ResArgs &a) {
     constexpr int RW = MODE == gk::RES_MGS ? RES_RW : RES_RW_HH;
     constexpr int LW = MODE == gk::RES_MGS ? RES_LW : RES_LW_HH;
-    constexpr int WBT = MODE == gk::RES_MGS ? gk::WB : gk::WB_HH;
+    constexpr int WBT = PIPE ? gk::PIPE_D : (MODE == gk::RES_MGS ? gk::WB : gk::WB_HH);
     static std::atomic<int> attr[ATTR_DEVS];
     if (c->dev < 0 || c->dev >= ATTR_DEVS) return set_err(GK_ERR_ARG, "device id %d out of range", c->dev);
     if (attr[c->dev].load() < p.lds) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gk::k_mgs_wres<RW, LW, MODE, WBT>),
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&gk::k_mgs_wres<RW, LW, MODE, WBT, PIPE>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
         attr[c->dev] = p.lds;
     }
-    gk::k_mgs_wres<RW, LW, MODE, WBT><<<p.G, gk::WT, p.lds, c->st>>>(a);
+    gk::k_mgs_wres<RW, LW, MODE, WBT, PIPE><<<p.G, gk::WT, p.lds, c->st>>>(a);
     LAUNCHCHK();
     return GK_OK;
 }
@@ -1049,7 +1072,17 @@ int launch_wres(gk_ctx *c, const ResPlan &p, const gk::ResArgs &a) {
     switch (a.mode) {
         case gk::RES_HH_UP: return launch_wres_m<gk::RES_HH_UP>(c, p, a);
         case gk::RES_HH_DOWN: return launch_wres_m<gk::RES_HH_DOWN>(c, p, a);
-        default: return launch_wres_m<gk::RES_MGS>(c, p, a);
+        default:
+            if constexpr (RES_PIPE_OK) {
+                if (p.pipe) {
+                    // the counted waits of the pipelined pass hold on full workgroups only
+                    if (p.r2e != RES_RW || p.l2e != RES_LW || (a.n & 1) || a.nres2 != a.n / 2)
+                        return set_err(GK_ERR_STATE, "pipelined w-only step on a plan that is not full (%d + %d chunks)",
+                                       p.r2e, p.l2e);
+                    return launch_wres_m<gk::RES_MGS, true>(c, p, a);
+                }
+            }
+            return launch_wres_m<gk::RES_MGS>(c, p, a);
     }
 }
 
@@ -2686,6 +2719,7 @@ int gk_set_tuning(gk_ctx *c, int key, int value) {
             break;
         case GK_TUNE_RES_LDS: c->tune_res_lds = value != 0; break;
         case GK_TUNE_RES_WONLY: c->tune_res_wonly = value < 0 ? -1 : (value != 0); break;
+        case GK_TUNE_RES_PIPE: c->tune_res_pipe = value < 0 ? -1 : (value != 0); break;
         case GK_TUNE_HH_FUSE: c->tune_hh_fuse = value != 0; break;
         case GK_TUNE_CHEB_STEN: c->tune_cheb_sten = value != 0; break;
         case GK_TUNE_SPIN_WAIT: c->tune_spin_wait = value != 0; break;

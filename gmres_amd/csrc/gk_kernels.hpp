@@ -1084,6 +1084,10 @@ __global__ __launch_bounds__(RT, 2) void k_mgs_res(ResArgs a) {
 // loaded with the default policy, so it is still in the Infinity Cache when
 // it is read again as V_i by the next projection (V_i itself non-temporal).
 // Same exchange, same arithmetic as k_mgs_res.
+// PIPE (MGS step, full workgroups only -- every one holds exactly RW + LW chunks, nothing
+// streamed; chosen by launch_wres): the pass keeps 14-16 column loads in flight through a
+// ring of WBT buffer pairs with counted waits instead of draining each batch of 16
+// (4096^2: pass 32.65 -> 31.16 us per projection, 251.8 -> 261.8 it/s).
 // --------------------------------------------------------------------------
 constexpr int WT = 256;  // threads per workgroup (4 waves, one per SIMD)
 #ifndef GK_RES_WB
@@ -1122,6 +1126,15 @@ constexpr int TOUCH = GK_RES_TOUCH;
 // 16 / 20 / 24 / 28 / 32 / 40 / 48 -> 41.47 / 41.08 / 41.04 / 40.78 / 41.17 / 42.7 / 43.6
 // us per projection (two boxes); Householder 24 vs 32: 40.76 vs 41.96 us per reflection.
 constexpr int TOUCH_MGS = GK_RES_TOUCH_MGS;
+// ... and of the MGS-R launches that run the software-pipelined pass (PIPE, below): its
+// shorter pass leaves the touched lines less time in L2 and the paced touch less of a wait
+// to fill.  A/B at 4096^2 on the pipelined build, three interleaved runs each
+// (profiles/r07/ab_pipe_touch_r07.jsonl): 8 / 12 / 16 / 20 / 28 / 36 -> 263.3 / 264.0 /
+// 264.6 / 264.8 / 258.4 / 247.2 it/s (36 on another box, where 28 gave 257.2).
+#ifndef GK_RES_TOUCH_MGS_PIPE
+#define GK_RES_TOUCH_MGS_PIPE 20
+#endif
+constexpr int TOUCH_MGS_PIPE = GK_RES_TOUCH_MGS_PIPE;
 // Load policy of the dot column V_q of a pass (A/B knob): 0 = default, so the
 // column is still in the Infinity Cache when the next pass reads it as its
 // AXPY column V_i; 1 = non-temporal like V_i (every column comes from HBM).
@@ -1149,8 +1162,27 @@ constexpr int TOUCH_PACE = GK_RES_TOUCH_PACE;
 // the reflection chains' pacing (0 = burst); re-measured after the depth / residency
 // re-tune (profiles/r02/ab_pace_retune.jsonl): 8 / 24 -> 41.06 / 41.1 vs 40.57 us burst
 constexpr int TOUCH_PACE_HH = GK_RES_TOUCH_PACE_HH;
+// Ring depth of the MGS step's software-pipelined pass (k_mgs_wres<.., PIPE>, below): chunks
+// whose two column loads are in flight.  10 still builds without scratch (244 AGPRs), 12
+// does not; A/B at 4096^2 (profiles/r07/ab_pipe_touch_r07.jsonl): 8 vs 10 -> 258.4 vs 260.7
+// it/s at touch depth 28, 264.8 vs 265.7 at 20 (samples overlap), so the ring stays at 8.
+#ifndef GK_RES_PIPE_D
+#define GK_RES_PIPE_D 8
+#endif
+constexpr int PIPE_D = GK_RES_PIPE_D;
 
-template <int RW, int LW, int MODE, int WBT = WB>
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>) in order: a loop
+// unrolled by construction, its index a constant in the body
+template <class F, int... I>
+__device__ __forceinline__ void seq_apply(F &&f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void seq_for(F &&f) {
+    seq_apply(f, std::make_integer_sequence<int, N>{});
+}
+
+template <int RW, int LW, int MODE, int WBT = WB, bool PIPE = false>
 __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
     extern __shared__ double2 lw[];  // [LW][WT]
     __shared__ double sm[WT / 64];
@@ -1163,7 +1195,7 @@ __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
     const int t = threadIdx.x;
     constexpr int mode = MODE;
     constexpr int PACE = MODE == RES_MGS ? TOUCH_PACE : TOUCH_PACE_HH;
-    constexpr int TCH = MODE == RES_MGS ? TOUCH_MGS : TOUCH;  // touched chunks per workgroup
+    constexpr int TCH = MODE == RES_MGS ? (PIPE ? TOUCH_MGS_PIPE : TOUCH_MGS) : TOUCH;  // touched chunks per workgroup
     const int j = a.j, np = res_np(mode, j);
     const i64 n2 = a.n >> 1, ld2 = a.ld >> 1;
     const i64 nch = a.nres2 / WT;
@@ -1192,9 +1224,9 @@ __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
         if ((a.n & 1) && blockIdx.x == gridDim.x - 1 && t == 0) a.w[a.n - 1] = (a.n - 1 == u) ? 1.0 : 0.0;
     } else {
 #pragma unroll
-        for (int k = 0; k < RW; ++k) wr[k] = (c0 + k < cend) ? W2[(c0 + k) * WT + t] : double2{0.0, 0.0};
+        for (int k = 0; k < RW; ++k) wr[k] = (PIPE || c0 + k < cend) ? W2[(c0 + k) * WT + t] : double2{0.0, 0.0};
         for (int k = 0; k < LW; ++k)
-            if (l0 + k < lend) lw[k * WT + t] = W2[(l0 + k) * WT + t];
+            if (PIPE || l0 + k < lend) lw[k * WT + t] = W2[(l0 + k) * WT + t];
     }
     // acc += the closing reduction of element pair e2 (local double2 index)
     auto red = [&](double &acc, const double2 &v, const double2 &b, int kind, i64 e2, bool chk) {
@@ -1207,11 +1239,92 @@ __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
     };
     // One pass over the slab: w -= ch V_i, then the reduction `kind`
     // (<w, V_q>, ||w(tail0:)||^2, or none).  Returns this thread's partial.
+    const i64 wc0 = c0, wl0 = l0;  // (a pass works on copies of its own)
     auto pass = [&](double ch, int i, int q, int kind) -> double {
         const double2 *__restrict__ A2 = V2 + (i64)i * ld2;
         const double2 *__restrict__ B2 = V2 + (i64)q * ld2;
         const bool dot = kind == RK_DOT;
         double acc = 0.0;
+        // (pipelined instantiation: the chunk origins opaque per pass, so that the chunk
+        // addresses are formed where they are used and not kept in registers across the passes)
+        i64 c0 = wc0, l0 = wl0;
+        if constexpr (PIPE) {
+            int zero = 0;
+            asm volatile("" : "+s"(zero));
+            c0 += zero;
+            l0 += zero;
+        }
+        if constexpr (PIPE) {
+            // Software-pipelined pass (every workgroup holds exactly RW + LW chunks, nothing
+            // streamed, n even: launch_wres).  The RW + LW chunks are walked in the same
+            // order -- registers, then LDS -- through a ring of D = WBT buffer pairs (the
+            // registers of the batch pass's av[] and bv[]): chunk k's two loads go into slot
+            // k mod D as soon as chunk k - D is consumed, so 2 (D - 1) to 2 D loads stay in
+            // flight through the whole pass.  The loads are asm statements, which the compiler
+            // does not count; every chunk issues exactly two (without a dot column the second
+            // one re-reads one resident chunk), loads return in issue order, so the counted
+            // wait before chunk k -- two for each younger chunk in flight -- retires exactly
+            // that chunk's pair.  The wait names the two buffers "+v": their arithmetic cannot
+            // be scheduled above it.  Loads and waits are unconditional, straight-line code: a
+            // branch around one would merge buffer values, and the compiler may place such a
+            // merge's copies ahead of the wait.
+            constexpr int D = WBT, NCH = RW + LW;
+            static_assert(MODE == RES_MGS && NCH > D && 2 * (D - 1) <= 63 && !RES_QNT,
+                          "pipelined pass: the MGS step, counts within vmcnt's 6 bits, V_q default policy");
+            d2v pa[D], pb[D];
+            const unsigned lo = (unsigned)t * (unsigned)sizeof(double2);
+            // the columns at the workgroup's register and LDS chunk ranges
+            const double2 *Ar = A2 + c0 * WT, *Al = A2 + l0 * WT, *Br = B2 + c0 * WT, *Bl = B2 + l0 * WT;
+            // nothing of the compiler's own is in flight from here on (it then adds no waits of
+            // its own inside the pass, which would drain the loads in flight)
+            __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
+            // always true here, and only around a chunk's arithmetic: the test puts every
+            // chunk's arithmetic in a block of its own, which is what holds the unrolled pass
+            // inside the register budget
+            auto held = [&](int k) { return k < RW ? c0 + k < cend : l0 + (k - RW) < lend; };
+            auto issue = [&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                // wave-uniform chunk bases
+                const double2 *ap = k < RW ? Ar + k * WT : Al + (k - RW) * WT;
+                const double2 *bq = k < RW ? Br + k * WT : Bl + (k - RW) * WT;
+                const double2 *bp = dot ? bq : Ar;
+                d2v &da = pa[k % D], &db = pb[k % D];
+                const unsigned off = lo;  // (named outside the asm operands: captured by the generic lambda)
+                asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "=v"(da) : "v"(off), "s"(ap));
+                asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(db) : "v"(off), "s"(bp));
+            };
+            auto wait = [&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                constexpr int younger = NCH - 1 - k < D - 1 ? NCH - 1 - k : D - 1;  // chunks in flight behind k
+                d2v &da = pa[k % D], &db = pb[k % D];
+                asm volatile("s_waitcnt vmcnt(%2)" : "+v"(da), "+v"(db) : "i"(2 * younger));
+            };
+            auto consume = [&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                const double2 av{pa[k % D].x, pa[k % D].y}, bv{pb[k % D].x, pb[k % D].y};
+                if (!held(k)) return;
+                if constexpr (k < RW) {
+                    wr[k].x = wr[k].x - ch * av.x;
+                    wr[k].y = wr[k].y - ch * av.y;
+                    red(acc, wr[k], bv, kind, (c0 + k) * WT + t, false);
+                } else {
+                    constexpr int kl = k - RW;
+                    double2 wv = lw[kl * WT + t];
+                    wv.x = wv.x - ch * av.x;
+                    wv.y = wv.y - ch * av.y;
+                    lw[kl * WT + t] = wv;
+                    red(acc, wv, bv, kind, (l0 + kl) * WT + t, false);
+                }
+            };
+            seq_for<D>(issue);
+            seq_for<NCH>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                wait(kc);
+                consume(kc);
+                if constexpr (k + D < NCH) issue(std::integral_constant<int, k + D>{});
+            });
+            return acc;
+        }
         // registers: batches of WBT chunks, both columns in flight (k0 a constant once unrolled)
         auto rbatch = [&](const int k0) {
             double2 av[WBT], bv[WBT];
@@ -1452,12 +1565,17 @@ __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
     }
     const double hn = sqrt(h);
     double2 *__restrict__ O2 = reinterpret_cast<double2 *>(a.vout);
+    if constexpr (PIPE) {  // (as in a pass: the chunk addresses formed here, not kept from the prologue)
+        int zero = 0;
+        asm volatile("" : "+s"(zero));
+        O2 += zero;
+    }
 #pragma unroll
     for (int k = 0; k < RW; ++k)
-        if (c0 + k < cend)
+        if (PIPE || c0 + k < cend)  // (the pipelined instantiation runs on full workgroups only)
             O2[(c0 + k) * WT + t] = hn != 0.0 ? double2{wr[k].x / hn, wr[k].y / hn} : double2{0.0, 0.0};
     for (int k = 0; k < LW; ++k)
-        if (l0 + k < lend) {
+        if (PIPE || l0 + k < lend) {
             const double2 v = lw[k * WT + t];
             O2[(l0 + k) * WT + t] = hn != 0.0 ? double2{v.x / hn, v.y / hn} : double2{0.0, 0.0};
         }

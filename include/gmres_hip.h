@@ -334,7 +334,7 @@ int gk_sync(gk_ctx *ctx);
  * info[GK_RES_INFO_LEN]: variant, workgroups G, R2, L2, prefetch, control
  * wave, w-only, non-temporal column loads, register / LDS chunks per
  * workgroup in use, dynamic LDS bytes, resident double2 of the slab, and
- * (unused, 0),
+ * whether the w-only MGS step runs its software-pipelined pass (GK_TUNE_RES_PIPE; 1 / 0),
  * (gk_res_info only) whether the Arnoldi step's Chebyshev(k) pass forms z = A v in its own
  * stage 0 (1 / 0; -1 on a multi-rank context whose smallest slab is not known
  * until its first solve), the threads per workgroup (= double2 per chunk), and the
@@ -389,6 +389,12 @@ int gk_res_info(gk_ctx *ctx, int hh, long long *info);
  *   GK_TUNE_RES_WONLY      large slabs: -1 (default) pick by the modelled bytes per projection,
  *                          1 always, 0 never the w-only variant (one wave per SIMD, ~490 registers
  *                          per lane: w in registers + LDS, both columns streamed)
+ *   GK_TUNE_RES_PIPE       the w-only MGS step's software-pipelined pass (the column loads of the
+ *                          next half-batch in flight while one is consumed; bit-identical
+ *                          results): -1 (default) the build's choice (GK_RES_PIPE), 1 on, 0 off.
+ *                          It runs only where every workgroup holds its full 89 + 39 chunks and
+ *                          nothing is streamed (4096^2 on 256 CUs); gk_res_info reports whether
+ *                          the launches run it (`pipe`)
  *   GK_TUNE_VERR_ORDER     1 (default): the v_err diagnostics (gk_mgs_verr, gk_hh_verr) use the
  *                          reference's dot_product order, one running sum per dot (bit-identical
  *                          to the reference's formula on the same basis; single rank); 0: tree
@@ -490,6 +496,7 @@ int gk_res_info(gk_ctx *ctx, int hh, long long *info);
 #define GK_TUNE_RES_PF 27
 #define GK_TUNE_SR_BLOCKS 28
 #define GK_TUNE_SR_TWO_LEVEL 29
+#define GK_TUNE_RES_PIPE 30
 int gk_set_tuning(gk_ctx *ctx, int key, int value);
 /* Test hook: hold = 1 enqueues on the context's stream a wait for a mapped host
  * word that only hold = 0 writes (hipStreamWaitValue32) -- every later kernel of
