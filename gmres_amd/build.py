@@ -26,17 +26,22 @@ HIP_SO = os.path.join(LIB, "libgmres_hip.so")
 FHOST_SO = os.path.join(LIB, "libgmres_fhost.so")
 DRIVER = os.path.join(LIB, "test_mfp_hip")
 
-# Translation units compiled in parallel: the C-ABI + every kernel but the
-# Chebyshev pass, and the Chebyshev pass split by level count (its many
-# unrolled instantiations dominate the build time).
-HIP_SOURCES = [os.path.join(CSRC, "gk_api.hip"), os.path.join(CSRC, "gk_cheb.hip"), os.path.join(CSRC, "gk_blk.hip")]
+# Translation units compiled in parallel, one per subsystem: the C-ABI and the
+# streaming kernels (gk_api), the Chebyshev pass split by level count, the blocked
+# and the strict resident steps (gk_blk, gk_resident), the collectives (gk_comm)
+# and the short-recurrence solvers (gk_sr_api).  Seconds per unit, one compile at
+# a time on an 8-core build machine: gk_api 7, gk_cheb0..3 26-31, gk_blk 15,
+# gk_resident 42-48 (the unrolled resident kernels), gk_comm 4, gk_sr_api 8; the
+# single gk_api unit they were split from took 47-60.
+HIP_SOURCES = [os.path.join(CSRC, f) for f in ("gk_api.hip", "gk_cheb.hip", "gk_blk.hip", "gk_resident.hip",
+                                                "gk_comm.hip", "gk_sr_api.hip")]
 # (source, extra defines, object name): the Chebyshev pass in GK_CF_PARTS parts
 GK_CF_PARTS = 4
 HIP_UNITS = ([(HIP_SOURCES[0], [], "gk_api.o")] + [(HIP_SOURCES[1], [f"GK_CF_PART={p}"], f"gk_cheb{p}.o")
                                                     for p in range(GK_CF_PARTS)]
-             + [(HIP_SOURCES[2], [], "gk_blk.o")])
+             + [(s, [], os.path.basename(s)[:-4] + ".o") for s in HIP_SOURCES[2:]])
 HIP_HEADERS = [os.path.join(CSRC, h) for h in ("gk_common.hpp", "gk_kernels.hpp", "gk_cheb.hpp", "gk_res.hpp",
-                                                "gk_blk.hpp", "gk_sr.hpp")]
+                                                "gk_blk.hpp", "gk_sr.hpp", "gk_host.hpp", "gk_resident.hpp")]
 HIP_DEPS = HIP_SOURCES + HIP_HEADERS + [os.path.join(ROOT, "include", "gmres_hip.h")]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall"]
 F_SOURCES = [os.path.join(FSRC, "gmres_hip.f90")]

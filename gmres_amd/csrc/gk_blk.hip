@@ -1,7 +1,7 @@
 // gk_blk.hip -- the blocked-projection MGS-R step (gk_blk.hpp): one all-gather
 // per block of S projections instead of one per projection.  Opt-in
 // (GK_TUNE_RES_BLOCK); the default stays the strict MGS-R step of
-// gmres_mgsr.f90:341-360 (k_mgs_wres / k_mgs_wpc / k_mgs_res, gk_kernels.hpp).
+// gmres_mgsr.f90:341-360 (k_mgs_wres / k_mgs_wpc / k_mgs_res, gk_resident.hip).
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -30,26 +30,15 @@ __device__ __forceinline__ double uniform(double v) {
 #define GK_BLK_POLL_SLEEP 16
 #endif
 constexpr int BLK_POLL_SLEEP = GK_BLK_POLL_SLEEP;
-#ifndef GK_BLK_REV2
-#define GK_BLK_REV2 1
-#endif
-constexpr bool BLK_REV2 = GK_BLK_REV2 != 0;  // the second sweep's blocks in reverse order (A/B knob)
-#ifndef GK_BLK_DOT_NT
-#define GK_BLK_DOT_NT 0
-#endif
-// 1: the dot columns of cached chunks non-temporal (they are held on chip from then
-// on); 0: the default policy, so a column read again within the Infinity Cache's
-// reach (the reversed second sweep, the next step's first sweep) is a hit (A/B knob)
-constexpr bool BLK_DOT_NT = GK_BLK_DOT_NT != 0;
-#ifndef GK_BLK_PF_SPLIT
-#define GK_BLK_PF_SPLIT 1
-#endif
-// the strict step on this kernel (S = 1, GK_TUNE_RES_PF): the prefetch during an all-gather
+// The second sweep walks its blocks in reverse order, and the dot columns of cached chunks
+// are read with the default policy, so a column read again within the Infinity Cache's
+// reach (the reversed second sweep, the next step's first sweep) is a hit; forward sweeps
+// with those columns non-temporal lost the A/B (profiles/r05/ab_blk_rev2_r05h.jsonl).
+// The strict step on this kernel (S = 1, GK_TUNE_RES_PF): the prefetch during an all-gather
 // from the waves that do not poll it, so the poll -- and on N ranks a rank-total pusher's push --
 // does not queue behind it (4-rank rehearsal 935 -> 968 it/s, single GPU +1 %:
 // profiles/r05/ab_strict_pf_split_r05aq.txt); blocks of 2 / 4 keep every wave its own
 // elements (a wash there: ab_blk_pf_split_r05ak.txt)
-constexpr bool BLK_PF_SPLIT = GK_BLK_PF_SPLIT != 0;
 #ifndef GK_BLK_WB_LDS
 #define GK_BLK_WB_LDS 2
 #endif
@@ -111,12 +100,12 @@ __global__ __launch_bounds__(NT, 1) void k_mgs_blk(ResArgs a) {
     const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
     const int j = a.j;
     const int nb1 = blk_sweep(j, S), P = 2 * nb1;
-    // the block pass p subtracts: the first sweep in column order, the second (REV2)
+    // the block pass p subtracts: the first sweep in column order, the second
     // in reverse -- its first block is the one the first sweep ended with (still on
     // chip), and the columns read last come back first (Infinity-Cache hits at the
     // split loads); in exact arithmetic the second sweep's h are all 0 in any order
     // (S = 1 is strict MGS-R: both sweeps in the reference's column order)
-    auto blk_of = [&](int p) { return p < nb1 ? p : (BLK_REV2 && S > 1 ? 2 * nb1 - 1 - p : p - nb1); };
+    auto blk_of = [&](int p) { return p < nb1 ? p : (S > 1 ? 2 * nb1 - 1 - p : p - nb1); };
     const i64 n2 = a.n >> 1, ld2 = a.ld >> 1;
     const i64 nch = a.nres2 / NT;
     const i64 c0 = (i64)blockIdx.x * a.r2e, cend = c0 + a.r2e < nch ? c0 + a.r2e : nch;
@@ -272,8 +261,6 @@ __global__ __launch_bounds__(NT, 1) void k_mgs_blk(ResArgs a) {
                     for (int d = 0; d < S; ++d) {
                         if (k < PFX)  // (the norm pass reads a stale but finite block here: unused)
                             bv[u][d] = lpf[(d * PFX + (k < PFX ? k : 0)) * NT + t];
-                        else if (k < RX + LX && BLK_DOT_NT)
-                            bv[u][d] = ldv<true>(at(D[d], cb + k));
                         else
                             bv[u][d] = ldv<false>(at(D[d], cb + k));
                     }
@@ -421,7 +408,7 @@ __global__ __launch_bounds__(NT, 1) void k_mgs_blk(ResArgs a) {
         }
         if (p + 2 < P) {  // the next pass reduces dots: its block's loads overlap this all-gather
             const int b2 = blk_of(p + 2);
-            prefetch(blk_lo(b2, S), blk_n(b2, S, j), BLK_PF_SPLIT && S == 1 ? K : NW);
+            prefetch(blk_lo(b2, S), blk_n(b2, S, j), S == 1 ? K : NW);
         }
         for (int v = wv; v < vend; v += NW) {
             double out = 0.0;
@@ -520,7 +507,6 @@ __global__ __launch_bounds__(NT, 1) void k_mgs_blk(ResArgs a) {
 }
 
 // ------------------------------------------------------------------ host ---
-#ifndef GK_BLK_KERNEL_ONLY  // (register-budget experiments instantiate one kernel themselves)
 #ifndef GK_BLK_TOUCH
 #define GK_BLK_TOUCH 28
 #endif
@@ -571,9 +557,6 @@ struct BlkCfg<2> {
                                             {32, 0, 1, 9, 512, 0}, {90, 38, 0, 0, 256, 0}};
     static constexpr int wb[BLK_NVAR] = {4, 4, 4, 2, 4};
 };
-#ifndef GK_BLK_S4_R8_1W
-#define GK_BLK_S4_R8_1W 1
-#endif
 // S = 4 at <= 8 chunks of 512 (the 4096^2 / 8 load): one wave per SIMD -- 16 chunks of w and
 // of each of the 4 cached columns in ~450 registers -- so that LDS is free for the first 8
 // chunks of the next dot block, prefetched during the all-gather (the two-wave build had no
@@ -582,9 +565,9 @@ struct BlkCfg<2> {
 template <>
 struct BlkCfg<4> {
     static constexpr BlkGeom g[BLK_NVAR] = {{4, 0, 4, 0, 512, pfx_cap(4, 4, 512)},
-                                            GK_BLK_S4_R8_1W ? BlkGeom{16, 0, 16, 0, 256, pfx_cap(8, 4, 256)} : BlkGeom{8, 0, 8, 0, 512, 0},
+                                            {16, 0, 16, 0, 256, pfx_cap(8, 4, 256)},
                                             {16, 0, 2, 4, 512, 0}, {32, 0, 0, 4, 512, 0}, {88, 38, 0, 0, 256, 0}};
-    static constexpr int wb[BLK_NVAR] = {4, GK_BLK_S4_R8_1W ? 4 : 2, 2, 1, 2};
+    static constexpr int wb[BLK_NVAR] = {4, 4, 2, 1, 2};
 };
 
 template <int S, int V>
@@ -593,14 +576,9 @@ int launch_v(const ResArgs &a, int G, int lds, int dev, hipStream_t st) {
     constexpr int WBT = BlkCfg<S>::wb[V];
     constexpr int TCH = V == BLK_WONLY ? BLK_TOUCH : 0;
     auto kern = &k_mgs_blk<g.rw, g.lw, g.rx, g.lx, S, WBT, TCH, g.nt, g.pfx>;
-    static std::atomic<int> attr[64];
-    if (dev < 0 || dev >= 64) return (int)hipErrorInvalidDevice;
-    if (lds > 0 && attr[dev].load() < lds) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        attr[dev] = lds;
-    }
+    static std::atomic<int> attr[ATTR_DEVS];
+    const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void *>(kern), dev, lds, attr);
+    if (e != hipSuccess) return (int)e;
     kern<<<G, g.nt, lds, st>>>(a);
     return (int)hipGetLastError();
 }
@@ -636,7 +614,5 @@ int blk_launch(int var, int S, const ResArgs &a, int G, int lds, int dev, hipStr
         default: return (int)hipErrorInvalidValue;
     }
 }
-
-#endif  // GK_BLK_KERNEL_ONLY
 
 }  // namespace gk

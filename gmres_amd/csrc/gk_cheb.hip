@@ -11,23 +11,12 @@
 
 namespace gk {
 
-// Scheduling barrier after every level (1) or only between time steps (0).
-#ifndef GK_CF_LVBAR
-#define GK_CF_LVBAR 0
-#endif
-constexpr bool CF_LVBAR = GK_CF_LVBAR != 0;
-
 // 4c - s as ONE fma: 4c is exact (a power-of-two scale), so fma(4, c, -s)
 // rounds the same real number once, exactly as (4c) - s does -- bit-identical
 // to the per-sweep kernel and the oracle, one FP64 instruction per point and
-// level fewer in the issue-bound level chain.  0: the multiply + subtract.
-#ifndef GK_CF_FMA4
-#define GK_CF_FMA4 1
-#endif
-__device__ __forceinline__ double cf_4c_minus(double c, double s) {
-    if (GK_CF_FMA4) return __builtin_fma(4.0, c, -s);
-    return 4.0 * c - s;
-}
+// level fewer in the issue-bound level chain (116.4 -> 110.7 us per pass against the
+// multiply + subtract, profiles/r06/ab_cf_fma4_r06bc.txt).
+__device__ __forceinline__ double cf_4c_minus(double c, double s) { return __builtin_fma(4.0, c, -s); }
 
 
 // Lane i gets lane i-1's value (lane 0 gets 0) / lane i+1's (lane 63 gets 0).
@@ -276,7 +265,6 @@ __global__ __launch_bounds__(CF_W) __attribute__((amdgpu_waves_per_eu(CF_OCC, CF
                 }
             }
             zcur = znext;
-            if (CF_LVBAR) __builtin_amdgcn_sched_barrier(0);
         }
         // the last level emitted row t - LL
         const int orow = t - LL;
@@ -384,21 +372,17 @@ int occupancy(K kern, int dev) {
 // minimises  rounds x (JT + 2L)  where a round is one wave of resident
 // workgroups (occupancy x CUs): at 4096^2, L = 8 (2 waves per SIMD) JT = 80
 // gives 1924 workgroups in ONE round where 64 would need two.
-// GK_CF_JTFINE (default): every even JT from 16 to 256 is a candidate, so the
-// one round fills the resident slots as tightly as the window count allows
-// (4096^2, L = 8: JT = 78, 2014 workgroups of 96 steps, where 80 gave 1976 of 98).
-#ifndef GK_CF_JTFINE
-#define GK_CF_JTFINE 1
-#endif
+// Every even JT from 16 to 256 is a candidate, so the one round fills the resident
+// slots as tightly as the window count allows (4096^2, L = 8: JT = 78, 2014 workgroups
+// of 96 steps, where a coarse list's 80 gave 1976 of 98: -2.5 %,
+// profiles/r06/ab_cf_jtfine_r06bj.txt).
 int pick_jt(int gx, int lines, int L, i64 cap) {
-    static const int jts_coarse[] = {16, 24, 32, 48, 64, 80, 96, 128, 160, 192, 256, 384, 512, 1024, 2048, 4096, 8192};
-    static const std::vector<int> jts_fine = [] {
+    static const std::vector<int> jts = [] {
         std::vector<int> v;
         for (int jt = 16; jt <= 256; jt += 2) v.push_back(jt);
         for (int jt : {384, 512, 1024, 2048, 4096, 8192}) v.push_back(jt);
         return v;
     }();
-    const std::vector<int> jts = GK_CF_JTFINE ? jts_fine : std::vector<int>(std::begin(jts_coarse), std::end(jts_coarse));
     i64 best = -1;
     int JT = GK_CF_JT > 0 ? GK_CF_JT : 64;
     for (int jt : jts) {

@@ -1,8 +1,14 @@
-// gk_common.hpp -- definitions shared by the kernel translation units
-// (gk_api.hip: everything but the Chebyshev pass; gk_cheb.hip: the pass).
+// gk_common.hpp -- definitions shared by every translation unit (gk_api.hip: the
+// context and the Arnoldi steps; gk_comm.hip: the collectives; gk_resident.hip and
+// gk_blk.hip: the resident steps; gk_sr_api.hip: the short-recurrence solvers;
+// gk_cheb.hip: the Chebyshev pass).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <type_traits>
+
+// host symbols of the gk namespace that other units call but the library does not export
+#define GK_HIDDEN __attribute__((visibility("hidden")))
 
 namespace gk {
 
@@ -61,7 +67,47 @@ __device__ __forceinline__ double2 ldg(const double2 *p) {
     return double2{t.x, t.y};
 }
 
+template <int VEC>
+__device__ __forceinline__ void ld_vec(const double *p, bool ok, double (&v)[VEC]) {
+    if (ok) {
+        if constexpr (VEC == 2) {
+            const double2 t = *reinterpret_cast<const double2 *>(p);
+            v[0] = t.x;
+            v[1] = t.y;
+        } else {
+            v[0] = p[0];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) v[k] = 0.0;
+    }
+}
+
+template <int VEC>
+__device__ __forceinline__ void st_vec(double *p, const double (&v)[VEC]) {
+    if constexpr (VEC == 2) {
+        *reinterpret_cast<double2 *>(p) = double2{v[0], v[1]};
+    } else {
+        p[0] = v[0];
+    }
+}
+
 // Fused reductions of a pass: none, <y, vdot>, or <y, y>.
 enum { ACC_NONE = 0, ACC_DOT = 1, ACC_NORM = 2 };
+
+// A kernel launched with `lds` bytes of dynamic LDS needs that size allowed first.
+// hipFuncSetAttribute is per device: memo[ATTR_DEVS] (one per kernel instantiation)
+// remembers the size set on each.  Returns a hipError_t (hipErrorInvalidDevice for a
+// device id outside the memo).
+constexpr int ATTR_DEVS = 64;
+inline hipError_t ensure_dyn_lds(const void *kernel, int dev, int lds, std::atomic<int> *memo) {
+    if (dev < 0 || dev >= ATTR_DEVS) return hipErrorInvalidDevice;
+    if (lds > 0 && memo[dev].load() < lds) {
+        const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+        memo[dev] = lds;
+    }
+    return hipSuccess;
+}
 
 }  // namespace gk

@@ -1,0 +1,237 @@
+// gk_host.hpp -- internal header of the host-side units of libgmres_hip.so
+// (gk_api.hip, gk_comm.hip, gk_sr_api.hip); never installed.  The context, the
+// error / check macros, the profiling scope and the few helpers that cross units.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>
+
+#include <condition_variable>
+#include <deque>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/gmres_hip.h"
+#include "gk_res.hpp"
+
+using gk::i64;
+
+namespace gk {
+struct SrDev;
+struct SrMirror;
+}  // namespace gk
+
+// In-process communicator: several contexts of one process (e.g. ranks
+// sharing one GPU in tests) driven by one host thread each.  Collectives are
+// a host barrier + HIP event ordering + device copies/sums; the message
+// pattern is exactly the RCCL one (same counts, same roots, same halos).
+struct gk_group {
+    int n = 0;
+    std::mutex mu;
+    std::condition_variable cv;
+    int arrived = 0;
+    long gen = 0;
+    bool broken = false;
+    std::vector<gk_ctx *> members;
+    std::vector<const double *> ptrs;
+};
+
+struct gk_ctx {
+    int dev = 0, N = 0, line0 = 0, nlines = 0, m = 0;
+    i64 nloc = 0, ld = 0, g0 = 0;
+    hipStream_t st = nullptr;
+    // HBM residents
+    double *V = nullptr;  // (m+1) columns, stride ld
+    double *w = nullptr, *z = nullptr, *aux = nullptr, *dA = nullptr, *dB = nullptr;
+    double *x = nullptr, *b = nullptr, *vj = nullptr, *hlo = nullptr, *hhi = nullptr;
+    double *dh = nullptr;  // deep halos of the Chebyshev pass inputs: [3 vectors][lo, hi][CF_HMAX lines][N]
+    double *zline = nullptr;  // N zeros (the short-recurrence marches' line past a physical boundary)
+    double *red = nullptr;   // NSLOT * NPMAX partial slabs
+    double *hcol = nullptr;  // m+2 Hessenberg column / scalars
+    double *ydev = nullptr;  // m+1
+    double *hb = nullptr;    // m+2 Householder broadcast buffer
+    double *scal = nullptr;  // 8 scalars
+    double *hcol_host = nullptr;  // pinned
+    double *hall = nullptr;       // device: per-step Hessenberg columns, m slots of m+2
+    double *hallh = nullptr;      // mapped pinned host mirror of hall (written by k_scale)
+    double *hallh_dev = nullptr;  // its device address
+    std::vector<hipEvent_t> ev_step;  // completion of step j
+    double *Vb = nullptr;    // Householder verr basis (lazy)
+    double *gram_slab = nullptr, *gram_out = nullptr;
+    short2 *gram_pairs = nullptr;
+    int gram_nblk = 0;
+    // preconditioner
+    int pkind = GK_PREC_IDENTITY, pdeg = 8;
+    double p0 = 8.2, p1 = 0.2;
+    // decomposition / comm
+    int nranks = 1, rank = 0, max_lines = 0;
+    int min_lines = 0;  // smallest slab of any rank (0: not gathered yet; ensure_min_lines)
+    ncclComm_t comm = nullptr;
+    bool comm_ok = false;
+    gk_group *lg = nullptr;  // in-process group (GK local comm), else RCCL
+    hipEvent_t lev_a = nullptr, lev_b = nullptr;
+    double *lscratch = nullptr;
+    // device exchange (xgmi back-end, gk_comm_init_xgmi / gk_xchg_*)
+    gk::u64 *xs_buf = nullptr;  // own receive region, uncached HBM
+    i64 xs_words = 0;
+    gk::XsPeers xs_peers{};     // every rank's region, mapped here
+    std::vector<void *> xs_mapped;
+    bool xs_ready = false, xs_on = false, xs_broken = false;
+    unsigned xs_seq = 0, xs_hseq = 0;
+    int *xs_err = nullptr, *xs_err_dev = nullptr;  // mapped pinned flag
+    long long xs_tick_per_ms = 100000;
+    int xs_timeout_ms = 20000;
+    gk::u64 xs_timeout = 0;
+    // resident MGS-R step (gk::k_mgs_res): one persistent launch per Arnoldi step
+    gk::u64 *res_gath = nullptr;                    // [RES_KMAX values][2][RGMAX][2] all-gather granules
+    double *res_gm = nullptr;                       // blocked step: the cycle's Gram table [m+1][RES_SMAX]
+    int tune_res_blk = 1;                           // blocked-projection MGS step: S (1 = strict MGS-R)
+    int tune_res_pf = 0;                            // strict MGS step on the blocked kernel's LDS prefetch (S = 1)
+    int pend_res_blk = 0, pend_res_pf = -1;         // requested mid-cycle: applied at the next cycle start
+    int watchdog_ms = 0;                            // host watchdog of stream waits (0: from the device deadlines)
+    bool broken = false;                            // the watchdog fired: a kernel of this context never completed
+    unsigned *hold_word = nullptr, *hold_word_dev = nullptr;  // gk_debug_hold_stream's mapped word
+    int *res_err = nullptr, *res_err_dev = nullptr;  // mapped deadline flag
+    unsigned res_tag = 1;                           // next granule tag (never 0)
+    int res_cus = 0;                                // compute units of the device
+    int tune_res = -1;                              // -1 auto, 0 off, 1 on where possible
+    int tune_res_r2 = 0;                            // cap of resident double2 per thread (0 = auto)
+    int tune_res_pipe = -1;                         // w-only MGS step: pipelined pass (-1: the build's default)
+    int tune_res_wonly = -1;                        // large slabs: w-only variant (-1: by the byte model)
+    int tune_verr_order = 1;                        // v_err diagnostics in the reference's dot order
+    int tune_hh_fuse = 1;                           // Householder step: small launches folded into the chains
+    int tune_hh_norm_order = 0;                     // Householder: the reflector norms in flang-rt's order (1 rank)
+    int res_share = 1;                              // contexts sharing this device's CUs
+    int res_timeout_ms = 20000;
+    bool res_broken = false;                        // a deadline was missed: launch path from then on
+    gk::u64 *res_stamps = nullptr;                  // gk_profile_res_split: [RGMAX][4] ticks per workgroup
+    bool res_split = false;
+    gk::u64 *res_trace = nullptr;                   // gk_profile_res_trace: [RGMAX][RES_TRACE_X][2] ticks
+    int res_trace_j = 0, res_trace_mode = -1;       // the traced launch: step j, mode (-1 = off)
+    int res_trace_g = 0, res_trace_np = 0;          // its workgroups and exchanges
+    // launch geometry
+    int vec = 2, JT = 16;
+    dim3 sgrid;
+    int sr_JT = 64, tune_sr_blocks = 0;  // the short-recurrence marches' geometry (gk_sr_*)
+    int tune_sr_two = 1;                 // GK_TUNE_SR_TWO_LEVEL
+    bool sr_two = false;                 // this solve runs the two-level marches (set by gk_sr_start)
+    dim3 sr_sgrid;
+    int np_sr = 0;
+    int np_st = 0, np_pj = 0, nblk_stream = 0;
+    int last_np = 0;          // partial count written by the last ACC-carrying sweep
+    int tune_cheb_fused = 1;  // temporal-blocked Chebyshev sweeps (single slab)
+    int tune_cheb_sten = 1;   // the Arnoldi step's pass forms z = A v itself (stage 0)
+    int tune_spin_wait = 1;   // the per-step host wait spins on its event (0: hipEventSynchronize)
+    int tune_graph = 1;       // launch-path MGS-R steps captured as hipGraphs (RCCL / no collective)
+    int tune_res_qdef = -1;   // k_mgs_res NT: V_q of the LDS / streamed parts with the default policy (-1 auto)
+    int tune_res_pc = -1;     // column-cache variant k_mgs_wpc: -1 by the byte model, 0 never, 1 where it fits
+    int tune_res_fold = 1;    // N ranks, device exchange: the first dot's rank hop inside the MGS step launch
+    std::vector<hipGraphExec_t> gstep;  // captured step j (launch path), valid for partial-slab count gkey
+    std::vector<unsigned> gxs;          // device exchanges in captured step j (their sequence numbers)
+    int gkey = -1;
+    unsigned graph_seq0 = 0;            // xs_seq when the capture in progress began
+    unsigned *xs_seqdev = nullptr;      // device: the sequence base of a replayed graph's exchanges
+    bool capturing = false;   // a step is being captured: no profiling events inside it
+    // tuning knobs (gk_set_tuning)
+    int tune_nt = -1, tune_pj_blocks = 0, tune_st_blocks = 0;  // tune_nt: -1 auto
+    bool nt_auto = false;
+    int prof_every = 1;       // record events in steps with j % prof_every == 0
+    bool prof_on_step = true;
+    // state
+    bool cycle_mgs = false, cycle_hh = false;
+    double beta0 = -1.0;
+    // profiling
+    bool prof = false;
+    std::vector<hipEvent_t> ev0, ev1;
+    std::vector<int> evk;
+    int nev = 0;
+    double prof_ms[GK_NKID] = {0};
+    long long prof_n[GK_NKID] = {0};
+    // fused short-recurrence solve (gk_sr_*)
+    gk::SrDev *sr_dev = nullptr;
+    gk::SrMirror *sr_mir = nullptr, *sr_mir_dev = nullptr;  // mapped pinned
+    double *sr_hist = nullptr;
+    int sr_hist_len = 0;
+    int sr_solver = -1, sr_par = 0, sr_queued = 0, sr_maxit = 0;
+    std::deque<hipEvent_t> sr_pend;   // end of each queued chunk, oldest first
+    std::vector<hipEvent_t> sr_evfree;
+    hipGraphExec_t sr_graph = nullptr;  // SR_GRAPH_ITERS iterations from parity 0
+};
+
+// Helpers shared by the host units: hidden, so the library exports only the C-ABI
+// (and the kernels).
+namespace gkh __attribute__((visibility("hidden"))) {
+
+extern thread_local std::string g_err;  // gk_last_error's text (gk_api.hip)
+int set_err(int code, const char *fmt, ...);
+
+#define HIPCHK(call)                                                                            \
+    do {                                                                                        \
+        hipError_t e_ = (call);                                                                 \
+        if (e_ != hipSuccess) return set_err(GK_ERR_HIP, "%s:%d %s: %s", __FILE__, __LINE__, #call, \
+                                             hipGetErrorString(e_));                            \
+    } while (0)
+#define NCCLCHK(call)                                                                           \
+    do {                                                                                        \
+        ncclResult_t r_ = (call);                                                               \
+        if (r_ != ncclSuccess) return set_err(GK_ERR_RCCL, "%s:%d %s: %s", __FILE__, __LINE__, #call, \
+                                              ncclGetErrorString(r_));                          \
+    } while (0)
+#define CHK(call)                      \
+    do {                               \
+        int s_ = (call);               \
+        if (s_ != GK_OK) return s_;    \
+    } while (0)
+#define LAUNCHCHK() HIPCHK(hipGetLastError())
+
+constexpr int NSLOT = 4;  // partial slabs (ping-pong + spares)
+constexpr int PROF_POOL = 8192;
+
+// gk_api.hip
+int prof_harvest(gk_ctx *c);
+void graph_reset(gk_ctx *c);
+void set_geometry(gk_ctx *c);
+int check_ctx(gk_ctx *c);
+int precond_sweeps(gk_ctx *c, double *out, int acc, const double *vdot, double *part);
+int fill_hash(gk_ctx *c, double *x, unsigned long long seed);  // k_fill_hash of the global index
+// The short-recurrence solvers keep their vectors in the Krylov columns and their
+// state on the device: any call that changes the operator data, the right-hand
+// side or x, or that starts a GMRES cycle (which overwrites the columns), ends the
+// running gk_sr_* solve -- later gk_sr_iterate / status / history refuse until the
+// next gk_sr_start.
+inline void sr_invalidate(gk_ctx *c) { c->sr_solver = -1; }
+
+// gk_comm.hip
+bool collective(const gk_ctx *c);
+void xs_set_timeout(gk_ctx *c, int ms);
+int xs_check(gk_ctx *c);
+int res_check(gk_ctx *c);
+int spin_until(gk_ctx *c, hipError_t (*query)(void *), void *obj, const char *what);
+hipError_t query_stream(void *s);
+hipError_t query_event(void *e);
+int sync_st(gk_ctx *c);
+int allreduce(gk_ctx *c, double *buf, int count, bool vec = false);
+int bcast(gk_ctx *c, double *buf, int count, int root);
+int halo_lines(gk_ctx *c, const double *vec, int nl, double *lo, double *hi);
+int halo(gk_ctx *c, const double *vec);
+const double *halo_lo(gk_ctx *c);
+const double *halo_hi(gk_ctx *c);
+
+struct ProfScope {
+    gk_ctx *c;
+    int slot = -1;
+    ProfScope(gk_ctx *c_, int kid) : c(c_) {
+        if (!c->prof || !c->prof_on_step || c->capturing) return;
+        if (c->nev == PROF_POOL) prof_harvest(c);
+        slot = c->nev++;
+        c->evk[slot] = kid;
+        (void)hipEventRecord(c->ev0[slot], c->st);
+    }
+    ~ProfScope() {
+        if (slot >= 0) (void)hipEventRecord(c->ev1[slot], c->st);
+    }
+};
+
+inline double *slot(gk_ctx *c, int s) { return c->red + (i64)s * gk::NPMAX; }
+
+}  // namespace gkh

@@ -1,5 +1,5 @@
 // gk_res.hpp -- device-side machinery shared by the resident MGS-R / Householder
-// step kernels (gk_kernels.hpp, gk_blk.hip): the device-exchange granule
+// step kernels (gk_resident.hip, gk_blk.hip): the device-exchange granule
 // primitives, ResArgs and the in-launch all-gather.  Only inline functions,
 // constants and types: included by more than one translation unit.
 #pragma once
@@ -277,13 +277,9 @@ static_assert(RES_NREP >= 1 && RES_NREP * XS_REP_STEP <= XS_MAXV, "replicas must
 // (profiles/r02/ab_rep_*.jsonl) 4 instead of 16: 4096^2 41.8 vs 41.5 us, but 2048^2 9.57
 // vs 9.66 and 1024^2 4.12 vs 4.28 -- a poll is cheaper once 32 readers share a copy.
 constexpr int RES_POLL_SLEEP = GK_RES_POLL_SLEEP;
-#ifndef GK_RES_PUSHER_FAST
-#define GK_RES_PUSHER_FAST 1
-#endif
-// N ranks: workgroup 0, which pushes the rank total to the peers once its sweep
-// completes, polls its granules without the sleep (its detection delay is on
+// N ranks: a workgroup that pushes the rank total to the peers once its sweep
+// completes polls its granules without the sleep (its detection delay is on
 // every rank's critical path; the other workgroups' is not).
-constexpr bool RES_PUSHER_FAST = GK_RES_PUSHER_FAST != 0;
 #ifndef GK_RES_PUSHERS
 #define GK_RES_PUSHERS 4
 #endif
@@ -438,7 +434,7 @@ __device__ __forceinline__ void res_exchange(const ResArgs &a, int p, const doub
                     if (lane == 0) xs_fail(a.err, XSE_RES_WG, miss);
                     break;
                 }
-                if (RES_PUSHER_FAST && res_pusher(a))
+                if (res_pusher(a))
                     __builtin_amdgcn_s_sleep(1);  // the rank-total pusher: push as soon as the sweep completes
                 else
                     __builtin_amdgcn_s_sleep(SLEEP);
@@ -539,7 +535,7 @@ __device__ __forceinline__ bool res_collect_v(const ResArgs &a, int p, int v, do
                     if (lane == 0) xs_fail(a.err, XSE_RES_WG, miss);
                     break;
                 }
-                if (RES_PUSHER_FAST && a.nranks > 1)
+                if (a.nranks > 1)
                     __builtin_amdgcn_s_sleep(1);  // a rank-total pusher
                 else
                     __builtin_amdgcn_s_sleep(SLEEP);

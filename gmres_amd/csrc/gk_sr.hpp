@@ -31,7 +31,7 @@
 // Element-wise expressions keep the reference's association order (compiled
 // with -ffp-contract=off); only the dot-product summation order differs.
 #pragma once
-#include "gk_kernels.hpp"  // ld_vec, st_vec
+#include "gk_common.hpp"  // ld_vec, st_vec
 
 namespace gk {
 

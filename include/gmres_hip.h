@@ -364,11 +364,13 @@ int gk_res_info(gk_ctx *ctx, int hh, long long *info);
  *                          non-temporal when a vector exceeds 48 MiB)
  *   GK_TUNE_PROJ_BLOCKS    workgroups of the projection kernel (0 = auto)
  *   GK_TUNE_STENCIL_BLOCKS target workgroups of the stencil sweeps (0 = auto)
- *   (keys 3, 17 and 26 -- the reversed projection walk, the w-only step's stencil
- *   prologue and the look-ahead blocked step -- were measured slower and removed in
- *   round 5; DESIGN.md 3.1 / 3.1c / 3.4 keep the numbers; they are unknown keys now)
- *   GK_TUNE_PROJ_BLOCKED   1: contiguous range per workgroup; 0: grid-stride
- *   GK_TUNE_PROJ_UNROLL    double2 loads in flight per thread and array: 2, 4, 8; 0 = auto
+ *   (retired keys, unknown now and never reused: 3, 17 and 26 -- the reversed projection
+ *   walk, the w-only step's stencil prologue and the look-ahead blocked step -- were
+ *   measured slower and removed in round 5, DESIGN.md 3.1 / 3.1c / 3.4 keep the numbers;
+ *   4, 5 and 12 -- the projection kernel's contiguous-range mapping, its forced unroll
+ *   (the auto rule stays: 4 loads in flight for one trip per thread or fewer, else 2) and
+ *   the switch that streamed what the pairs variant holds in LDS -- recorded no win and
+ *   nothing set them)
  *   GK_TUNE_CHEB_FUSED     1 (default): Chebyshev(k <= 8) as temporal-blocked passes of up to
  *                          4 sweeps each (single slab, even N); 0: one launch per sweep
  *   GK_TUNE_XCHG_TIMEOUT_MS deadline of one device-exchange wait (default 20000)
@@ -383,9 +385,6 @@ int gk_res_info(gk_ctx *ctx, int hh, long long *info);
  *                          workgroups; gk_comm_init_local sets it to the group size)
  *   GK_TUNE_RES_TIMEOUT_MS deadline of one in-launch wait (default 20000); a miss fails the step
  *                          with GK_ERR_COMM and switches the context to the launch path
- *   GK_TUNE_RES_LDS        1 (default): when the slab exceeds the register-resident part, keep w
- *                          of 144 KiB more per workgroup in LDS (16 B/unknown per projection
- *                          instead of 32); 0: stream it
  *   GK_TUNE_RES_WONLY      large slabs: -1 (default) pick by the modelled bytes per projection,
  *                          1 always, 0 never the w-only variant (one wave per SIMD, ~490 registers
  *                          per lane: w in registers + LDS, both columns streamed)
@@ -426,8 +425,7 @@ int gk_res_info(gk_ctx *ctx, int hh, long long *info);
  *                          before it; 0: the launch
  *   GK_TUNE_RES_PC         column-cache variant (GK_RES_WCOL): -1 (default) where its modelled
  *                          bytes per projection are fewer than both the pairs and the w-only
- *                          variants' (two-wave build; a one-wave build, GK_RES_PC_NT=256,
- *                          needs at most 2/3 of them); 0 never; 1 wherever the slab fits
+ *                          variants'; 0 never; 1 wherever the slab fits
  *   GK_TUNE_RES_BLOCK      1 (default): the strict MGS-R step (gmres_mgsr.f90:341-360), one
  *                          in-launch all-gather per projection; 2 or 4 (opt-in): the blocked
  *                          step k_mgs_blk -- the projections of each sweep in blocks of S
@@ -472,15 +470,12 @@ int gk_res_info(gk_ctx *ctx, int hh, long long *info);
 #define GK_TUNE_PROJ_NT 0
 #define GK_TUNE_PROJ_BLOCKS 1
 #define GK_TUNE_STENCIL_BLOCKS 2
-#define GK_TUNE_PROJ_BLOCKED 4
-#define GK_TUNE_PROJ_UNROLL 5
 #define GK_TUNE_CHEB_FUSED 6
 #define GK_TUNE_XCHG_TIMEOUT_MS 7
 #define GK_TUNE_RES 8
 #define GK_TUNE_RES_R2 9
 #define GK_TUNE_RES_SHARE 10
 #define GK_TUNE_RES_TIMEOUT_MS 11
-#define GK_TUNE_RES_LDS 12
 #define GK_TUNE_RES_WONLY 13
 #define GK_TUNE_VERR_ORDER 14
 #define GK_TUNE_HH_FUSE 15

@@ -245,6 +245,10 @@ def test_blocked_knob_rejects_other_sizes():
         assert c.res_info(hh=True)["blk"] == 1  # the reflection chains stay strict
         with pytest.raises(Exception, match="unknown tuning key"):  # the look-ahead build (removed, round 5)
             c.tune(26, 1)
+        # the projection kernel's blocked mapping / unroll knobs and the pairs variant's LDS switch (retired)
+        for key in (4, 5, 12):
+            with pytest.raises(Exception, match="unknown tuning key"):
+                c.tune(key, 1)
 
 
 
