@@ -42,6 +42,9 @@ GK_TUNE_WATCHDOG_MS = 24
 GK_TUNE_HH_NORM_ORDER = 25
 GK_TUNE_RES_PF = 27
 GK_TUNE_RES_PIPE = 30
+GK_TUNE_RIGHT_FUSED = 31
+GK_SIDE_LEFT, GK_SIDE_RIGHT = 0, 1
+GK_ERR_ARG, GK_ERR_STATE = -1, -4
 GK_PREC_IDENTITY, GK_PREC_CBPR2, GK_PREC_CHEB = 0, 1, 2
 (GK_KID_PROJ, GK_KID_STENCIL, GK_KID_SCALE, GK_KID_UPDATE, GK_KID_COMM, GK_KID_OTHER, GK_KID_RES, GK_KID_PREC,
  GK_KID_HALO, GK_KID_GRAPH) = range(10)
@@ -96,6 +99,7 @@ _SIGS = {
     "gk_xchg_enable": (c_int, [c_vp, c_int]),
     "gk_xchg_selftest": (c_int, [c_vp, c_int]),
     "gk_set_precond": (c_int, [c_vp, c_int, _dp, c_int, c_int]),
+    "gk_set_precond_side": (c_int, [c_vp, c_int]),
     "gk_set_rhs": (c_int, [c_vp, _dp]),
     "gk_set_rhs_ones": (c_int, [c_vp]),
     "gk_rhs_norm": (c_int, [c_vp, _dp]),

@@ -162,6 +162,56 @@ int stencil(gk_ctx *c, int op, int acc, gk::StArgs a) {
     }
 }
 
+// cbpr2 coefficients exactly as chebyshev.f90:19-25
+void cbpr2_coefs(const gk_ctx *c, double *d_out, double *alpha_out) {
+    const double em = c->p0, eM = c->p1;
+    const double cc = (eM - em) / 2.0;
+    const double d = (eM + em) / 2.0;
+    double alpha = 1.0 / d;
+    double beta = cc * alpha / 2.0;
+    beta = beta * beta;
+    alpha = 1.0 / (d - beta);
+    *d_out = d;
+    *alpha_out = alpha;
+}
+
+// The one-launch route of w = A (M^-1 v) (gk::k_right_cbpr2): cbpr2 on one rank
+// that holds the whole grid -- the march has no halo lines, the level-1 value of a
+// neighbour's line would need two of its lines.  Everything else takes the
+// two-launch route (GK_TUNE_RIGHT_FUSED 0 forces it).
+bool right_fused_ok(const gk_ctx *c) {
+    return c->tune_right_fused != 0 && c->pkind == GK_PREC_CBPR2 && c->nranks == 1 && c->line0 == 0 &&
+           c->nlines == c->N;
+}
+
+template <int VEC>
+int launch_right_v(gk_ctx *c, int acc, const gk::RcArgs &a) {
+    if (acc == gk::ACC_DOT)
+        gk::k_right_cbpr2<VEC, gk::ACC_DOT><<<c->sgrid, gk::TPB, 0, c->st>>>(a);
+    else
+        gk::k_right_cbpr2<VEC, gk::ACC_NONE><<<c->sgrid, gk::TPB, 0, c->st>>>(a);
+    LAUNCHCHK();
+    return GK_OK;
+}
+
+// out = A (cbpr2 v) in one launch; acc = ACC_DOT leaves <out, vdot> in slab `part`
+// (np_st partials, k_stencil's layout).
+int right_cbpr2(gk_ctx *c, const double *v, double *out, int acc, const double *vdot, double *part) {
+    if (acc != gk::ACC_NONE && acc != gk::ACC_DOT) return set_err(GK_ERR_ARG, "right_cbpr2: reduction %d", acc);
+    ProfScope ps(c, GK_KID_STENCIL);
+    if (acc != gk::ACC_NONE) c->last_np = c->np_st;
+    gk::RcArgs a{};
+    a.v = v;
+    a.w = out;
+    a.vdot = vdot;
+    a.part = part;
+    cbpr2_coefs(c, &a.d, &a.alpha);
+    a.N = c->N;
+    a.nlines = c->nlines;
+    a.JT = c->JT;
+    return c->vec == 2 ? launch_right_v<2>(c, acc, a) : launch_right_v<1>(c, acc, a);
+}
+
 template <bool NT, int U>
 void launch_proj_u(gk_ctx *c, int mode, double *w, const double *va, const double *vb, const double *pin,
                    int npin, double *pout, double *hslot, double coef, i64 tail0, int hstore) {
@@ -368,9 +418,10 @@ int launch_cf(gk_ctx *c, int L, int acc, gk::CFArgs &a, i64 *np, bool sten = fal
 }
 
 // Chebyshev(k <= 16) as one or two temporal-blocked passes (gk_cheb.hip):
-// sweeps 1..min(k, 8) in the first, the rest in the second.
-int cheb_fused(gk_ctx *c, double *out, int acc, const double *vdot, double *part, const double *c1,
-               const double *c2, double theta, const double *sten_v) {
+// sweeps 1..min(k, 8) in the first, the rest in the second.  The input is `in`, or
+// with sten_v the vector whose stencil image stage 0 forms.
+int cheb_fused(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part,
+               const double *c1, const double *c2, double theta, const double *sten_v) {
     ProfScope ps(c, GK_KID_PREC);
     const int k = c->pdeg;
     const int g1 = std::min(k, gk::CF_LMAX), g2 = k - g1;
@@ -390,7 +441,7 @@ int cheb_fused(gk_ctx *c, double *out, int acc, const double *vdot, double *part
     a.N = c->N;
     a.nlines = c->nlines;
     a.theta = theta;
-    a.din = sten ? sten_v : c->z;
+    a.din = sten ? sten_v : in;
     a.vdot = vdot;
     a.part = part;
     CHK(deep(a, 0, a.din, g1 + (sten ? 1 : 0)));
@@ -488,22 +539,17 @@ int cheb_coefs(gk_ctx *c, double *c1, double *c2, double *theta) {
     return GK_OK;
 }
 
-// out = M^-1 z for z already in c->z (cbpr2 or Chebyshev sweeps).
-int precond_sweeps(gk_ctx *c, double *out, int acc, const double *vdot, double *part) {
+// out = M^-1 in (cbpr2 or Chebyshev sweeps); `in` is read in place (in != out, and
+// for Chebyshev neither is one of the sweeps' work vectors aux, dA, dB).
+int precond_sweeps(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part) {
     bool fused = false;
     if (c->pkind == GK_PREC_CHEB) CHK(cheb_fused_ok(c, &fused));
-    if (!fused) CHK(halo(c, c->z));  // the fused passes bring their own deep halos
+    if (!fused) CHK(halo(c, in));  // the fused passes bring their own deep halos
     if (c->pkind == GK_PREC_CBPR2) {
-        // cbpr2 coefficients exactly as chebyshev.f90:19-25
-        const double em = c->p0, eM = c->p1;
-        const double cc = (eM - em) / 2.0;
-        const double d = (eM + em) / 2.0;
-        double alpha = 1.0 / d;
-        double beta = cc * alpha / 2.0;
-        beta = beta * beta;
-        alpha = 1.0 / (d - beta);
+        double d, alpha;
+        cbpr2_coefs(c, &d, &alpha);
         gk::StArgs b2{};
-        b2.x = c->z;
+        b2.x = in;
         b2.y = out;
         b2.vdot = vdot;
         b2.part = part;
@@ -520,7 +566,7 @@ int precond_sweeps(gk_ctx *c, double *out, int acc, const double *vdot, double *
     if (fused) {
         double c1[2 * gk::CF_LMAX], c2[2 * gk::CF_LMAX], th;
         CHK(cheb_coefs(c, c1, c2, &th));
-        return cheb_fused(c, out, acc, vdot, part, c1, c2, th, nullptr);
+        return cheb_fused(c, in, out, acc, vdot, part, c1, c2, th, nullptr);
     }
     double *dcur = c->dA, *dnext = c->dB;
     for (int it = 0; it < c->pdeg; ++it) {
@@ -534,7 +580,7 @@ int precond_sweeps(gk_ctx *c, double *out, int acc, const double *vdot, double *
         s.vdot = vdot;
         s.part = part;
         if (it == 0) {
-            s.x = c->z;
+            s.x = in;
             s.s1 = theta;
             s.o_res = last ? nullptr : c->aux;
             s.o_d = last ? nullptr : dcur;
@@ -569,7 +615,7 @@ int op_precond_sten(gk_ctx *c, const double *v, double *out, int acc, const doub
     if (!fused || (collective(c) && c->nranks > 1 && c->min_lines < c->pdeg + 1)) return GK_OK;
     double c1[2 * gk::CF_LMAX], c2[2 * gk::CF_LMAX], theta;
     CHK(cheb_coefs(c, c1, c2, &theta));
-    CHK(cheb_fused(c, out, acc, vdot, part, c1, c2, theta, v));
+    CHK(cheb_fused(c, nullptr, out, acc, vdot, part, c1, c2, theta, v));
     *done = true;
     return GK_OK;
 }
@@ -599,7 +645,36 @@ int op_precond(gk_ctx *c, const double *v, double *out, bool resid, int acc, con
     a.in1 = c->b;
     a.y = c->z;
     CHK(stencil(c, resid ? gk::OP_RESID : gk::OP_PLAIN, gk::ACC_NONE, a));
-    return precond_sweeps(c, out, acc, vdot, part);
+    return precond_sweeps(c, c->z, out, acc, vdot, part);
+}
+
+// out = b - A x, fused with its norm: the cycle start of right preconditioning (and
+// of the identity preconditioner).  np_st partials in `part`.
+int resid_norm(gk_ctx *c, double *out, double *part) {
+    CHK(halo(c, c->x));
+    gk::StArgs a{};
+    a.x = c->x;
+    a.in1 = c->b;
+    a.y = out;
+    a.part = part;
+    return stencil(c, gk::OP_RESID, gk::ACC_NORM, a);
+}
+
+// out = A (M^-1 v), the right-preconditioned Arnoldi operator (M not the identity),
+// with the fused reduction `acc` (none, or the dot with vdot) on the launch that
+// writes out.  One launch where k_right_cbpr2 applies; else z = M^-1 v by the
+// preconditioner's own route (N ranks: halo of v, the sweeps, halo of z) and the
+// plain stencil.
+int op_right(gk_ctx *c, const double *v, double *out, int acc, const double *vdot, double *part) {
+    if (right_fused_ok(c)) return right_cbpr2(c, v, out, acc, vdot, part);
+    CHK(precond_sweeps(c, v, c->z, gk::ACC_NONE, nullptr, nullptr));
+    CHK(halo(c, c->z));
+    gk::StArgs a{};
+    a.x = c->z;
+    a.y = out;
+    a.vdot = vdot;
+    a.part = part;
+    return stencil(c, gk::OP_PLAIN, acc, a);
 }
 
 int owner_of(gk_ctx *c, i64 gidx) {
@@ -957,6 +1032,16 @@ int gk_set_precond(gk_ctx *c, int kind, const double *params, int nparams, int d
     return GK_OK;
 }
 
+int gk_set_precond_side(gk_ctx *c, int side) {
+    CHK(check_ctx(c));
+    if (side != GK_SIDE_LEFT && side != GK_SIDE_RIGHT) return set_err(GK_ERR_ARG, "bad preconditioning side %d", side);
+    sr_invalidate(c);
+    c->cycle_mgs = c->cycle_hh = false;  // the open cycle's basis belongs to the other operator
+    if (side != c->side) graph_reset(c);
+    c->side = side;
+    return GK_OK;
+}
+
 int gk_set_rhs(gk_ctx *c, const double *b) {
     CHK(check_ctx(c));
     sr_invalidate(c);
@@ -1065,7 +1150,10 @@ int gk_mgs_cycle_start(gk_ctx *c, double *beta) {
         set_geometry(c);
         graph_reset(c);
     }
-    CHK(op_precond(c, c->x, c->w, true, gk::ACC_NORM, nullptr, slot(c, 0)));
+    if (right_prec(c))  // w = b - A x: the Arnoldi residual is the true residual
+        CHK(resid_norm(c, c->w, slot(c, 0)));
+    else
+        CHK(op_precond(c, c->x, c->w, true, gk::ACC_NORM, nullptr, slot(c, 0)));
     CHK(allreduce(c, slot(c, 0), c->last_np));
     CHK(scale(c, c->V, c->w, slot(c, 0), c->last_np, c->hcol));
     CHK(d2h_sync(c, beta, c->hcol, 1));
@@ -1087,8 +1175,11 @@ int gk_mgs_step_async(gk_ctx *c, int j) {
     const int s0 = 0;
     ResPlan rp;
     const bool res = res_plan(c, rp);
-    // w = M^-1 A V(:,j), fused with the first dot <w, V(:,1)>
-    CHK(op_precond(c, V + (i64)(j - 1) * ld, c->w, false, gk::ACC_DOT, V, slot(c, s0)));
+    // w = M^-1 A V(:,j) (side right: A M^-1 V(:,j)), fused with the first dot <w, V(:,1)>
+    if (right_prec(c))
+        CHK(op_right(c, V + (i64)(j - 1) * ld, c->w, gk::ACC_DOT, V, slot(c, s0)));
+    else
+        CHK(op_precond(c, V + (i64)(j - 1) * ld, c->w, false, gk::ACC_DOT, V, slot(c, s0)));
     int np = c->last_np;
     if (res) {  // the whole cascade + norm + scale as one resident launch
         // N ranks on the device exchange: the first dot's rank totals inside the launch
@@ -1164,9 +1255,19 @@ int gk_update_x(gk_ctx *c, const double *y, int n_out) {
     if (n_out < 1 || n_out > c->m) return set_err(GK_ERR_ARG, "bad n_out %d", n_out);
     HIPCHK(hipSetDevice(c->dev));
     HIPCHK(hipMemcpyAsync(c->ydev, y, sizeof(double) * n_out, hipMemcpyHostToDevice, c->st));
-    {
+    if (right_prec(c)) {  // x += M^-1 (V y): t = V y in w, M^-1 t in z
+        {
+            ProfScope ps(c, GK_KID_UPDATE);
+            gk::k_update_x<false><<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->w, c->V, c->ld, c->ydev, n_out, c->nloc);
+            LAUNCHCHK();
+        }
+        CHK(precond_sweeps(c, c->w, c->z, gk::ACC_NONE, nullptr, nullptr));
         ProfScope ps(c, GK_KID_UPDATE);
-        gk::k_update_x<<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->x, c->V, c->ld, c->ydev, n_out, c->nloc);
+        gk::k_add<<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->x, c->z, c->nloc);
+        LAUNCHCHK();
+    } else {
+        ProfScope ps(c, GK_KID_UPDATE);
+        gk::k_update_x<true><<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->x, c->V, c->ld, c->ydev, n_out, c->nloc);
         LAUNCHCHK();
     }
     CHK(sync_st(c));
@@ -1224,6 +1325,9 @@ int gk_hh_cycle_start(gk_ctx *c, int precondition, double *g1) {
     HIPCHK(hipSetDevice(c->dev));
     if (c->nranks > 1 && c->rank == 0 && c->nloc < c->m + 2)
         return set_err(GK_ERR_ARG, "Householder path needs the first slab to hold m+2 unknowns");
+    if (precondition && right_prec(c))
+        return set_err(GK_ERR_STATE, "Householder GMRES preconditions on the left only: "
+                                     "gk_set_precond_side(ctx, GK_SIDE_LEFT) first");
     if (precondition) {
         CHK(op_precond(c, c->x, c->w, true, gk::ACC_NORM, nullptr, slot(c, 0)));
     } else {
@@ -1267,6 +1371,9 @@ int gk_hh_step_async(gk_ctx *c, int j, int precondition) {
     CHK(check_ctx(c));
     if (j < 1 || j > c->m) return set_err(GK_ERR_ARG, "step j=%d outside 1..%d", j, c->m);
     if (!c->cycle_hh) return set_err(GK_ERR_STATE, "gk_hh_step before gk_hh_cycle_start");
+    if (precondition && right_prec(c))
+        return set_err(GK_ERR_STATE, "Householder GMRES preconditions on the left only: "
+                                     "gk_set_precond_side(ctx, GK_SIDE_LEFT) first");
     HIPCHK(hipSetDevice(c->dev));
     const i64 ld = c->ld;
     double *P = c->V;
@@ -1451,7 +1558,7 @@ int gk_apply(gk_ctx *c, int what, const double *in, double *out) {
         if (c->pkind == GK_PREC_IDENTITY) {
             HIPCHK(hipMemcpyAsync(c->w, c->z, sizeof(double) * c->nloc, hipMemcpyDeviceToDevice, c->st));
         } else {
-            CHK(precond_sweeps(c, c->w, gk::ACC_NONE, nullptr, nullptr));
+            CHK(precond_sweeps(c, c->z, c->w, gk::ACC_NONE, nullptr, nullptr));
         }
     }
     HIPCHK(hipMemcpyAsync(out, c->w, sizeof(double) * c->nloc, hipMemcpyDeviceToHost, c->st));
@@ -1512,6 +1619,7 @@ int gk_set_tuning(gk_ctx *c, int key, int value) {
                 c->tune_res_pf = value != 0;
             break;
         case GK_TUNE_VERR_ORDER: c->tune_verr_order = value != 0; break;
+        case GK_TUNE_RIGHT_FUSED: c->tune_right_fused = value != 0; break;
         case GK_TUNE_RES_TIMEOUT_MS:
             if (value < 1) return set_err(GK_ERR_ARG, "timeout must be >= 1 ms");
             c->res_timeout_ms = value;
@@ -1793,7 +1901,7 @@ int gk_precond_apply(int nside, int kind, const double *params, int degree, cons
             c.aux = scratch;
             c.dA = scratch ? scratch + n : nullptr;
             c.dB = scratch ? scratch + 2 * n : nullptr;
-            rc = precond_sweeps(&c, z, gk::ACC_NONE, nullptr, nullptr);
+            rc = precond_sweeps(&c, c.z, z, gk::ACC_NONE, nullptr, nullptr);
         }
     }
     c.z = c.aux = c.dA = c.dB = nullptr;
@@ -1936,11 +2044,13 @@ int gk_vec_count(gk_ctx *c, int *count) {
 int gk_vec_apply(gk_ctx *c, int what, int in, int out) {
     CHK(check_ctx(c));
     double *vi = vec_of(c, in), *vo = vec_of(c, out);
-    if (vi == nullptr || vo == nullptr || in == out || (what != 0 && what != 1))
+    if (vi == nullptr || vo == nullptr || in == out || what < 0 || what > 2)
         return set_err(GK_ERR_ARG, "bad gk_vec_apply(%d, %d, %d)", what, in, out);
     HIPCHK(hipSetDevice(c->dev));
     c->cycle_mgs = c->cycle_hh = false;
-    if (what == 0) {
+    if (what == 2 && c->pkind != GK_PREC_IDENTITY)  // out = A M^-1 in, the right-preconditioned step's operator
+        return op_right(c, vi, vo, gk::ACC_NONE, nullptr, nullptr);
+    if (what != 1) {  // A in (what = 2 with the identity preconditioner is A itself)
         CHK(halo(c, vi));
         gk::StArgs a{};
         a.x = vi;
@@ -1952,7 +2062,7 @@ int gk_vec_apply(gk_ctx *c, int what, int in, int out) {
         return GK_OK;
     }
     HIPCHK(hipMemcpyAsync(c->z, vi, sizeof(double) * c->nloc, hipMemcpyDeviceToDevice, c->st));
-    return precond_sweeps(c, vo, gk::ACC_NONE, nullptr, nullptr);
+    return precond_sweeps(c, c->z, vo, gk::ACC_NONE, nullptr, nullptr);
 }
 
 int gk_vec_dot(gk_ctx *c, int a, int b, double *result) {

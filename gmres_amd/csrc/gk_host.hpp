@@ -63,6 +63,8 @@ struct gk_ctx {
     // preconditioner
     int pkind = GK_PREC_IDENTITY, pdeg = 8;
     double p0 = 8.2, p1 = 0.2;
+    int side = GK_SIDE_LEFT;   // MGS-R: left (the reference) or right preconditioning (gk_set_precond_side)
+    int tune_right_fused = 1;  // side right, cbpr2, one rank: w = A M^-1 v as one march (k_right_cbpr2)
     // decomposition / comm
     int nranks = 1, rank = 0, max_lines = 0;
     int min_lines = 0;  // smallest slab of any rank (0: not gathered yet; ensure_min_lines)
@@ -192,7 +194,7 @@ int prof_harvest(gk_ctx *c);
 void graph_reset(gk_ctx *c);
 void set_geometry(gk_ctx *c);
 int check_ctx(gk_ctx *c);
-int precond_sweeps(gk_ctx *c, double *out, int acc, const double *vdot, double *part);
+int precond_sweeps(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part);
 int fill_hash(gk_ctx *c, double *x, unsigned long long seed);  // k_fill_hash of the global index
 // The short-recurrence solvers keep their vectors in the Krylov columns and their
 // state on the device: any call that changes the operator data, the right-hand
@@ -200,6 +202,8 @@ int fill_hash(gk_ctx *c, double *x, unsigned long long seed);  // k_fill_hash of
 // running gk_sr_* solve -- later gk_sr_iterate / status / history refuse until the
 // next gk_sr_start.
 inline void sr_invalidate(gk_ctx *c) { c->sr_solver = -1; }
+// Householder GMRES and the short-recurrence solvers precondition on the left only.
+inline bool right_prec(const gk_ctx *c) { return c->side == GK_SIDE_RIGHT && c->pkind != GK_PREC_IDENTITY; }
 
 // gk_comm.hip
 bool collective(const gk_ctx *c);

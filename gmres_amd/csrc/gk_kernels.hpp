@@ -219,6 +219,8 @@ __global__ __launch_bounds__(TPB) void k_finalize(const double *__restrict__ pin
 
 // x[e] += sum_k V[k*ld + e] * y[k]  (gmres_mgsr.f90:400-406: the reference's
 // row-wise dot_product(V(idx,1:n_out), y) with idx on the lane, k sequential).
+// ADD = false: x[e] = that sum (t = V y of the right-preconditioned update).
+template <bool ADD = true>
 __global__ __launch_bounds__(TPB) void k_update_x(double *__restrict__ x, const double *__restrict__ V,
                                                   i64 ld, const double *__restrict__ y, int nout, i64 n) {
     const i64 n2 = n >> 1;
@@ -233,15 +235,15 @@ __global__ __launch_bounds__(TPB) void k_update_x(double *__restrict__ x, const 
             s0 = s0 + v.x * yk;
             s1 = s1 + v.y * yk;
         }
-        double2 xv = X2[e];
-        xv.x = xv.x + s0;
-        xv.y = xv.y + s1;
+        double2 xv = ADD ? X2[e] : double2{0.0, 0.0};
+        xv.x = ADD ? xv.x + s0 : s0;
+        xv.y = ADD ? xv.y + s1 : s1;
         X2[e] = xv;
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         double s = 0.0;
         for (int k = 0; k < nout; ++k) s = s + V[(i64)k * ld + n - 1] * y[k];
-        x[n - 1] = x[n - 1] + s;
+        x[n - 1] = ADD ? x[n - 1] + s : s;
     }
 }
 
@@ -513,6 +515,182 @@ __global__ __launch_bounds__(TPB) void k_stencil(StArgs a) {
                 rp[k] = rn[k];
                 tp[k] = tn[k];
             }
+        }
+    }
+    if (ACC != ACC_NONE) {
+        const double s = block_sum(acc, sm);
+        if (threadIdx.x == 0) a.part[(i64)blockIdx.y * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// --------------------------------------------------------------------------
+// The right-preconditioned Arnoldi operator with cbpr2, w = A (M^-1 v), as ONE
+// line march (single rank, the whole grid): z = M^-1 v is never stored.
+//
+// Two levels in k_stencil's register scheme.  Level 1 (z, OP_CBPR2's exact
+// expressions: t = v/d, z = t + alpha*(v - A t)) runs one line ahead of level 2
+// (w = A z), so level 2 finds lines j-1, j, j+1 of z in registers; level 1 keeps
+// lines j, j+1, j+2 of v.  Per unknown: v and the dot partner read, w written
+// (24 B) where OP_CBPR2 + OP_PLAIN move 40 B.
+//
+// Window seams: a lane's level-2 W/E neighbour at a wave edge is a level-1 value
+// of the next window, which needs v two columns out -- lanes 0 and 63 compute the
+// level-1 value of the column next to their window themselves, from the two edge
+// columns ea (next to the window) and eb (one further), as k_sr_march2 does.
+// Line-tile seams: z of lines j0-1 and j1 is recomputed from v of lines
+// j0-2 .. j1+1.  Outside the grid z is ZERO (A z drops the neighbour), not cbpr2
+// of zero-padded v; v outside the grid is zero as in k_stencil.
+// Every expression, the stencil's association order and the per-workgroup dot
+// order are those of k_stencil on the same grid: w, and the partial slab, are
+// bit-identical to OP_CBPR2 followed by OP_PLAIN.
+// --------------------------------------------------------------------------
+struct RcArgs {
+    const double *v;    // operand, nlines*N (nlines == N: no halo lines)
+    double *w;          // output
+    const double *vdot; // ACC_DOT partner vector
+    double *part;       // partial slab (ACC_DOT)
+    double d, alpha;    // cbpr2 coefficients (chebyshev.f90:19-25)
+    int N, nlines, JT;
+};
+
+template <int VEC, int ACC>
+__global__ __launch_bounds__(TPB) void k_right_cbpr2(RcArgs a) {
+    __shared__ double sm[WAVES];
+    const int N = a.N, nl = a.nlines;
+    const int lane = threadIdx.x & 63;
+    const i64 i0 = (i64)blockIdx.x * (TPB * VEC) + (i64)VEC * threadIdx.x;
+    const bool act = i0 < N;
+    const int j0 = blockIdx.y * a.JT;
+    const int j1 = min(j0 + a.JT, nl);
+    const double dv = a.d, ca = a.alpha;
+    const bool e0 = lane == 0, e63 = lane == 63;
+    // edge columns of the window (lane 0: to its left, lane 63: to its right), clamped
+    // into the line; a clamped column is one whose value is never used (grid edge)
+    i64 ea = e0 ? i0 - 1 : i0 + VEC;
+    i64 eb = e0 ? i0 - 2 : i0 + VEC + 1;
+    const bool edge = (e0 || e63) && act;
+    const bool eb_ok = e0 ? (i0 - 2 >= 0) : (i0 + VEC + 1 < N);
+    ea = ea < 0 ? 0 : (ea >= N ? N - 1 : ea);
+    eb = eb < 0 ? 0 : (eb >= N ? N - 1 : eb);
+
+    // level-0 line: v (r), t = v/d at the own points, at ea (ra, ta) and at eb (tb)
+    struct L0 {
+        double r[VEC], t[VEC], ra, ta, tb;
+    };
+    struct Raw {
+        double r[VEC], ra, rb;
+    };
+    auto raw = [&](int jj, Raw &o) {
+        const bool lv = jj >= 0 && jj < nl;
+        const double *p = a.v + (i64)(lv ? jj : 0) * N;
+        ld_vec<VEC>(p + (act ? i0 : 0), act && lv, o.r);
+        o.ra = (edge && lv) ? p[ea] : 0.0;
+        o.rb = (edge && lv && eb_ok) ? p[eb] : 0.0;
+    };
+    auto form = [&](const Raw &q, L0 &o) {
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            o.r[k] = q.r[k];
+            o.t[k] = q.r[k] / dv;
+        }
+        o.ra = q.ra;
+        o.ta = q.ra / dv;
+        o.tb = q.rb / dv;
+    };
+    // level-1 line: z at the own points and at ea
+    struct L1 {
+        double z[VEC], za;
+    };
+    // z of line jj from v of lines jj-1 (us), jj (uc), jj+1 (un)
+    auto lev1 = [&](int jj, const L0 &us, const L0 &uc, const L0 &un, L1 &o) {
+        double left = __shfl_up(uc.t[VEC - 1], 1, 64);
+        double right = __shfl_down(uc.t[0], 1, 64);
+        left = e0 ? uc.ta : left;
+        right = e63 ? uc.ta : right;
+        left = i0 == 0 ? 0.0 : left;
+        right = i0 + VEC >= N ? 0.0 : right;
+        const bool lv = jj >= 0 && jj < nl;
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) {
+            const double W = (k == 0) ? left : uc.t[k - 1];
+            const double E = (k == VEC - 1) ? right : uc.t[k + 1];
+            const double s = ((W + E) + un.t[k]) + us.t[k];
+            const double ax = 4.0 * uc.t[k] - 1.0 * s;
+            const double z = uc.t[k] + ca * (uc.r[k] - ax);
+            o.z[k] = (lv && act) ? z : 0.0;
+        }
+        // the point ea: lane 0 -> W = eb, E = own point 0; lane 63 -> W = own point VEC-1, E = eb
+        const double Wa = e0 ? uc.tb : uc.t[VEC - 1];
+        const double Ea = e0 ? uc.t[0] : uc.tb;
+        const double sa = ((Wa + Ea) + un.ta) + us.ta;
+        const double axa = 4.0 * uc.ta - 1.0 * sa;
+        const double za = uc.ta + ca * (uc.ra - axa);
+        o.za = lv ? za : 0.0;
+    };
+
+    double acc = 0.0;
+    if (j0 < nl) {
+        L0 u0, u1, u2;  // v of lines j, j+1, j+2
+        L1 zm, zc;      // z of lines j-1, j
+        {
+            Raw q0, q1, q2, q3, q4;
+            raw(j0 - 2, q0);
+            raw(j0 - 1, q1);
+            raw(j0, q2);
+            raw(j0 + 1, q3);
+            raw(j0 + 2, q4);
+            L0 um2, um1;
+            form(q0, um2);
+            form(q1, um1);
+            form(q2, u0);
+            form(q3, u1);
+            form(q4, u2);
+            lev1(j0 - 1, um2, um1, u0, zm);
+            lev1(j0, um1, u0, u1, zc);
+        }
+        for (int j = j0; j < j1; ++j) {
+            // in flight while line j is computed: v of line j+3 (unused past the tile's
+            // last line) and the dot partner of line j
+            Raw qn;
+            if (j + 1 < j1) {
+                raw(j + 3, qn);
+            } else {
+#pragma unroll
+                for (int k = 0; k < VEC; ++k) qn.r[k] = 0.0;
+                qn.ra = qn.rb = 0.0;
+            }
+            const i64 row = (i64)j * N;
+            double vd[VEC];
+            if (ACC == ACC_DOT) ld_vec<VEC>(a.vdot + row + (act ? i0 : 0), act, vd);
+            L1 zp;  // z of line j+1
+            lev1(j + 1, u0, u1, u2, zp);
+            // level 2 at line j
+            double left = __shfl_up(zc.z[VEC - 1], 1, 64);
+            double right = __shfl_down(zc.z[0], 1, 64);
+            left = e0 ? zc.za : left;
+            right = e63 ? zc.za : right;
+            left = i0 == 0 ? 0.0 : left;
+            right = i0 + VEC >= N ? 0.0 : right;
+            double yv[VEC];
+#pragma unroll
+            for (int k = 0; k < VEC; ++k) {
+                const double W = (k == 0) ? left : zc.z[k - 1];
+                const double E = (k == VEC - 1) ? right : zc.z[k + 1];
+                const double s = ((W + E) + zp.z[k]) + zm.z[k];
+                yv[k] = 4.0 * zc.z[k] - 1.0 * s;
+            }
+            if (act) {
+                st_vec<VEC>(a.w + row + i0, yv);
+                if (ACC == ACC_DOT) {
+#pragma unroll
+                    for (int k = 0; k < VEC; ++k) acc = acc + yv[k] * vd[k];
+                }
+            }
+            zm = zc;
+            zc = zp;
+            u0 = u1;
+            u1 = u2;
+            form(qn, u2);
         }
     }
     if (ACC != ACC_NONE) {

@@ -133,11 +133,7 @@ int sr_march2(gk_ctx *c, gk::SrArgs a, int fin) {
 // out = M^-1 in by the generic preconditioner sweeps (Chebyshev(k)); with vdot
 // the last sweep's dot <out, vdot> feeds finaliser `fin`.
 int sr_prec(gk_ctx *c, const double *in, double *out, const double *vdot, int fin) {
-    double *keep = c->z;
-    c->z = const_cast<double *>(in);  // precond_sweeps reads its input from c->z
-    const int rc = precond_sweeps(c, out, vdot != nullptr ? gk::ACC_DOT : gk::ACC_NONE, vdot, slot(c, 0));
-    c->z = keep;
-    CHK(rc);
+    CHK(precond_sweeps(c, in, out, vdot != nullptr ? gk::ACC_DOT : gk::ACC_NONE, vdot, slot(c, 0)));
     if (fin == gk::FIN_NONE) return GK_OK;
     return sr_fin_after(c, fin, c->last_np, false);
 }
@@ -334,6 +330,9 @@ int gk_sr_start(gk_ctx *c, int solver, double tol, int max_iter) {
     if (solver != GK_SR_PCG && solver != GK_SR_BICGSTAB) return set_err(GK_ERR_ARG, "bad solver %d", solver);
     if (max_iter < 0 || max_iter > (1 << 28)) return set_err(GK_ERR_ARG, "bad max_iter %d", max_iter);
     if (c->m < 7) return set_err(GK_ERR_ARG, "short-recurrence solvers need a context with m >= 7 (vectors)");
+    if (right_prec(c))
+        return set_err(GK_ERR_STATE, "the short-recurrence solvers precondition on the left only: "
+                                     "gk_set_precond_side(ctx, GK_SIDE_LEFT) first");
     HIPCHK(hipSetDevice(c->dev));
     CHK(sr_drain(c));
     c->cycle_mgs = c->cycle_hh = false;  // the Krylov columns are the solver's vectors now

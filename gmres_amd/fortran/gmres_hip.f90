@@ -24,6 +24,7 @@ module gmres_hip_c
     implicit none
     integer(c_int), parameter :: GK_OK = 0
     integer(c_int), parameter :: GK_PREC_IDENTITY = 0, GK_PREC_CBPR2 = 1, GK_PREC_CHEB = 2
+    integer(c_int), parameter :: GK_SIDE_LEFT = 0, GK_SIDE_RIGHT = 1
     integer(c_int), parameter :: GK_VEC_X = 0, GK_VEC_B = 1
     integer(c_int), parameter :: GK_SR_PCG = 0, GK_SR_BICGSTAB = 1
     integer(c_int), parameter :: GK_LC_COPY = 0, GK_LC_AXPY = 1, GK_LC_AXPY2 = 2, GK_LC_XPAYMZ = 3, GK_LC_ZERO = 4
@@ -51,6 +52,11 @@ module gmres_hip_c
             type(c_ptr), value :: ctx
             integer(c_int), value :: kind, nparams, degree
             real(c_double), intent(in) :: params(*)
+        end function
+        integer(c_int) function gk_set_precond_side(ctx, side) bind(C, name='gk_set_precond_side')
+            import :: c_int, c_ptr
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: side
         end function
         integer(c_int) function gk_set_rhs(ctx, b) bind(C, name='gk_set_rhs')
             import :: c_int, c_ptr, c_double
@@ -291,6 +297,7 @@ module gmres_hip
     integer, parameter, public :: MGSR_OMP = 1, MGSR_MF = 0
 
     public :: stencil_vector, precond
+    public :: GK_SIDE_LEFT, GK_SIDE_RIGHT
     public :: hip_poisson5, hip_identity, hip_cbpr2, hip_chebyshev
     public :: gmres_mgsr_hip, gmres_hh_hip, gmres_hh_prec_hip, hip_release
     public :: pcg_hip, pbicgstab_hip, pcg_drive, bicgstab_drive, pcg_drive_seq, bicgstab_drive_seq
@@ -809,18 +816,25 @@ contains
         end if
     end subroutine prec_kind
 
-    type(c_ptr) function solver_ctx(b, m, kind, degree, params) result(ctx)
+    !> A solver's context.  The side is set on every call (left when absent), so
+    !> no solve inherits another's: only gmres_mgsr_hip passes one.
+    type(c_ptr) function solver_ctx(b, m, kind, degree, params, side) result(ctx)
         real(8), intent(in) :: b(:), params(:)
         integer, intent(in) :: m
         integer(c_int), intent(in) :: kind, degree
+        integer(c_int), intent(in), optional :: side
         integer :: nsize
+        integer(c_int) :: sd
         real(8) :: p(2)
+        sd = GK_SIDE_LEFT
+        if (present(side)) sd = side
         nsize = grid_side(size(b))
         p = 0.0d0
         if (size(params) >= 2) p = params(1:2)
         call gk_require(gk_create(int(hip_device, c_int), int(nsize, c_int), 0_c_int, int(nsize, c_int), &
                                   int(m, c_int), ctx), 'gk_create')
         call gk_require(gk_set_precond(ctx, kind, p, 2_c_int, degree), 'gk_set_precond')
+        call gk_require(gk_set_precond_side(ctx, sd), 'gk_set_precond_side')
         call gk_require(gk_set_rhs(ctx, b), 'gk_set_rhs')
     end function solver_ctx
 
@@ -828,8 +842,12 @@ contains
 
     !> Drop-in for gmres_mgsr_omp (src/gmres_mgsr.f90:277-288), same argument
     !> list; Ax_vec must be hip_poisson5 and M_inv one of the hip_* plug-ins.
-    !> Optional variant = MGSR_MF reproduces gmres_mgsr_mf (:98-109).
-    subroutine gmres_mgsr_hip(Ax_vec, b, x, m, tol, final_err, v_err, n_out, restart_out, M_inv, params, variant)
+    !> Optional variant = MGSR_MF reproduces gmres_mgsr_mf (:98-109).  Optional
+    !> side = GK_SIDE_RIGHT preconditions on the right (w = A M^-1 v_j,
+    !> x += M^-1 V y): final_err(j) is then the true relative residual, where the
+    !> reference's left side reports ||M^-1 (b - A x)|| / ||b||.
+    subroutine gmres_mgsr_hip(Ax_vec, b, x, m, tol, final_err, v_err, n_out, restart_out, M_inv, params, variant, &
+                              side)
         procedure(stencil_vector) :: Ax_vec
         real(8), intent(in) :: b(:)
         real(8), allocatable, intent(out) :: x(:)
@@ -839,17 +857,19 @@ contains
         integer, intent(out) :: n_out, restart_out
         procedure(precond) :: M_inv
         real(8), intent(in) :: params(:)
-        integer, intent(in), optional :: variant
+        integer, intent(in), optional :: variant, side
         type(c_ptr) :: ctx
-        integer(c_int) :: kind, degree
+        integer(c_int) :: kind, degree, sd
         integer :: var, ncyc
         real(8) :: dummy_h(1), dummy_f(1, 1)
         call require_device_op(Ax_vec, 'gmres_mgsr_hip')
         call prec_kind(M_inv, params, kind, degree)
         var = MGSR_OMP
         if (present(variant)) var = variant
+        sd = GK_SIDE_LEFT
+        if (present(side)) sd = int(side, c_int)
         allocate (x(size(b)), final_err(m), v_err(m + 1))
-        ctx = solver_ctx(b, m, kind, degree, params)
+        ctx = solver_ctx(b, m, kind, degree, params, sd)
         call gk_require(mgsr_drive(ctx, m, tol, norm2(b), var, hip_max_restarts, x, final_err, v_err, n_out, &
                                    restart_out, .true., .false., dummy_h, dummy_f, ncyc), 'gmres_mgsr_hip')
         call gk_require(gk_destroy(ctx), 'gk_destroy')

@@ -4,23 +4,33 @@
 !! lines; the only source change a reference user makes is the call names:
 !!   stvec -> hip_poisson5, cbpr2 -> hip_cbpr2,
 !!   gmres_hh_prec_omp -> gmres_hh_prec_hip, gmres_mgsr_omp -> gmres_mgsr_hip.
+!! An optional third argument `right` runs the MGS-R solve alone, preconditioned
+!! on the right (side = GK_SIDE_RIGHT: its "Final residual" is the true one).
 program test_mfp_hip
     use gmres_hip
     implicit none
     integer :: nsize, max_iter, n_args
     character(len=32) :: arg_str
+    logical :: right
     n_args = command_argument_count()
     if (n_args < 2) then
-        print *, "usage ./test_mfp_hip <grid size> <iterations per restart>"
+        print *, "usage ./test_mfp_hip <grid size> <iterations per restart> [right]"
         stop
+    end if
+    right = .false.
+    if (n_args >= 3) then
+        call get_command_argument(3, arg_str)
+        right = trim(arg_str) == 'right'
     end if
     call get_command_argument(1, arg_str)
     read (arg_str, *) nsize
     call get_command_argument(2, arg_str)
     read (arg_str, *) max_iter
     write (*, '(60("-"))')
-    call run(nsize, max_iter, .true.)
-    write (*, '(60("-"))')
+    if (.not. right) then
+        call run(nsize, max_iter, .true.)
+        write (*, '(60("-"))')
+    end if
     call run(nsize, max_iter, .false.)
     write (*, '(60("-"))')
     call hip_release()
@@ -38,6 +48,8 @@ contains
         call hip_poisson5(x, b, nsize)   ! b = A*1: every solution entry must be 1.0
         if (householder) then
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (Householder Chebyshev, MI355X)'
+        else if (right) then
+            write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR Chebyshev on the right, MI355X)'
         else
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR Chebyshev, MI355X)'
         end if
@@ -45,6 +57,9 @@ contains
         call system_clock(c0, crate)
         if (householder) then
             call gmres_hh_prec_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params)
+        else if (right) then
+            call gmres_mgsr_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params, &
+                                side=GK_SIDE_RIGHT)
         else
             call gmres_mgsr_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params)
         end if

@@ -19,6 +19,7 @@ from . import _native as nat
 
 PREC = {"identity": nat.GK_PREC_IDENTITY, "none": nat.GK_PREC_IDENTITY,
         "cbpr2": nat.GK_PREC_CBPR2, "cheb": nat.GK_PREC_CHEB, "chebyshev": nat.GK_PREC_CHEB}
+SIDE = {"left": nat.GK_SIDE_LEFT, "right": nat.GK_SIDE_RIGHT}
 MGSR_MF, MGSR_OMP = 0, 1
 
 
@@ -89,6 +90,7 @@ class Context:
         self.line0 = int(line0)
         self.nlines = int(N if nlines is None else nlines)
         self.nranks, self.rank = 1, 0
+        self.side = "left"
         h = nat.c_vp()
         nat.check(nat.hip().gk_create(self.device, self.N, self.line0, self.nlines, self.m, ctypes.byref(h)),
                   "gk_create")
@@ -183,10 +185,19 @@ class Context:
         return True
 
     # -- problem setup ---------------------------------------------------
-    def set_precond(self, kind: str | int = "identity", params=(8.2, 0.2), degree: int = 8) -> None:
+    def set_precond(self, kind: str | int = "identity", params=(8.2, 0.2), degree: int = 8,
+                    side: str = "left") -> None:
+        """side "left" (the reference's MGS-R) or "right": w = A M^-1 v_j and
+        x += M^-1 (V y), so final_err is the true relative residual
+        (gk_set_precond_side; MGS-R only)."""
         k = PREC[kind] if isinstance(kind, str) else int(kind)
+        if side not in SIDE:
+            raise ValueError(f"side must be 'left' or 'right', not {side!r}")
         pr = np.ascontiguousarray(params, dtype=np.float64)
         nat.check(nat.hip().gk_set_precond(self._h, k, _p(pr), pr.size, int(degree)), "gk_set_precond")
+        if side != self.side:  # a change of side ends an open cycle; the same side is no call at all
+            nat.check(nat.hip().gk_set_precond_side(self._h, SIDE[side]), "gk_set_precond_side")
+            self.side = side
 
     def set_rhs(self, b_local: np.ndarray) -> None:
         b = np.ascontiguousarray(b_local, dtype=np.float64).reshape(-1)
@@ -227,6 +238,12 @@ class Context:
         out = np.empty(self.nloc)
         nat.check(nat.hip().gk_apply(self._h, what, _p(vin), _p(out)), "gk_apply")
         return out
+
+    def vec_apply(self, what: int, src: int, dst: int) -> None:
+        """Operator on context-resident vectors (gk_vec_apply; ids 0 = x, 1 = b,
+        2 .. m+2 = the Krylov columns): what 0: dst = A src, 1: dst = M^-1 src,
+        2: dst = A M^-1 src."""
+        nat.check(nat.hip().gk_vec_apply(self._h, int(what), int(src), int(dst)), "gk_vec_apply")
 
     def true_residual(self) -> float:
         v = ctypes.c_double()

@@ -157,6 +157,29 @@ int gk_comm_latency(gk_ctx *ctx, int iters, double *allreduce_us, double *halo_u
 /* Preconditioner: kind GK_PREC_*, params (cbpr2: params[0..1] as
  * chebyshev.f90:19-25; CHEB: interval ends params[0..1]), degree (CHEB only). */
 int gk_set_precond(gk_ctx *ctx, int kind, const double *params, int nparams, int degree);
+/* Side of the preconditioner in the MGS-R cycle (context state; default left; kept
+ * across gk_set_precond).
+ *   GK_SIDE_LEFT   the reference: w = M^-1 A V(:,j), and the host's stopping quantity
+ *                  |g(j+1)| / ||b|| is the PRECONDITIONED residual ||M^-1 (b - A x)||
+ *                  over the unpreconditioned ||b|| (gmres_mgsr.f90:307,383).
+ *   GK_SIDE_RIGHT  w = A M^-1 V(:,j), x += M^-1 (V y): the Arnoldi residual is the
+ *                  true residual b - A x, so |g(j+1)| / ||b|| is what gk_true_residual
+ *                  returns, to rounding.  gk_mgs_cycle_start takes w = b - A x
+ *                  without the preconditioner; the cascade, norm and scale of a step
+ *                  are unchanged (resident launch, hipGraph and launch path all
+ *                  apply); gk_update_x forms t = V y, applies M^-1 and adds.  With
+ *                  the identity preconditioner both sides run the same launches
+ *                  (bit-identical).  A M^-1 v runs as ONE launch for cbpr2 on one
+ *                  rank (GK_TUNE_RIGHT_FUSED), else as the preconditioner's own
+ *                  launches followed by the stencil.
+ * Setting the side ends a running gk_sr_* solve and an open GMRES cycle (steps
+ * return GK_ERR_STATE until the next cycle start).  Householder GMRES and the
+ * short-recurrence solvers precondition on the left only: with side right and a
+ * preconditioner other than the identity, gk_hh_cycle_start / gk_hh_step_async with
+ * precondition = 1 and gk_sr_start return GK_ERR_STATE. */
+#define GK_SIDE_LEFT 0
+#define GK_SIDE_RIGHT 1
+int gk_set_precond_side(gk_ctx *ctx, int side);
 /* Right-hand side b (local part, host) or b = A*1 built on device
  * (the manufactured RHS of every reference driver, test_poisson_mf.f90:39-40). */
 int gk_set_rhs(gk_ctx *ctx, const double *b_local);
@@ -243,7 +266,9 @@ int gk_lanczos_bounds(gk_ctx *ctx, int k, double *lmin, double *lmax);
 #define GK_LC_XPAYMZ 3 /* out = a + s1*(b - s2*c)  */
 #define GK_LC_ZERO 4   /* out = 0                  */
 int gk_vec_count(gk_ctx *ctx, int *count);
-/* what = 0: out = A in; what = 1: out = M^-1 in (in != out). */
+/* what = 0: out = A in; what = 1: out = M^-1 in; what = 2: out = A M^-1 in, the
+ * operator of a right-preconditioned step by the step's own route (whatever the
+ * context's side is); in != out. */
 int gk_vec_apply(gk_ctx *ctx, int what, int in, int out);
 /* result = <a, b> over all ranks (synchronous). */
 int gk_vec_dot(gk_ctx *ctx, int a, int b, double *result);
@@ -465,6 +490,11 @@ int gk_res_info(gk_ctx *ctx, int hh, long long *info);
  *                          next to it in one two-level march (PCG 2 passes per iteration,
  *                          BiCGSTAB 3); 0: one pass each (3 / 5).  Bit-identical results;
  *                          read by gk_sr_start
+ *   GK_TUNE_RIGHT_FUSED    1 (default): side right with cbpr2 on one rank forms w = A M^-1 v in
+ *                          one two-level line march (k_right_cbpr2: v and the dot partner
+ *                          read, w written, z = M^-1 v never stored); 0: the route of N ranks
+ *                          and of Chebyshev(k) -- the preconditioner's launch, then the
+ *                          stencil.  Bit-identical w
  *   GK_TUNE_SPIN_WAIT      1 (default): gk_mgs_step_wait / gk_hh_step_wait spin on the step's
  *                          event; 0: hipEventSynchronize (may sleep in the driver per step) */
 #define GK_TUNE_PROJ_NT 0
@@ -492,6 +522,7 @@ int gk_res_info(gk_ctx *ctx, int hh, long long *info);
 #define GK_TUNE_SR_BLOCKS 28
 #define GK_TUNE_SR_TWO_LEVEL 29
 #define GK_TUNE_RES_PIPE 30
+#define GK_TUNE_RIGHT_FUSED 31
 int gk_set_tuning(gk_ctx *ctx, int key, int value);
 /* Test hook: hold = 1 enqueues on the context's stream a wait for a mapped host
  * word that only hold = 0 writes (hipStreamWaitValue32) -- every later kernel of
