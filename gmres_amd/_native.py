@@ -43,6 +43,7 @@ GK_TUNE_HH_NORM_ORDER = 25
 GK_TUNE_RES_PF = 27
 GK_TUNE_RES_PIPE = 30
 GK_TUNE_RIGHT_FUSED = 31
+GK_TUNE_RES_PIPE_CARRY = 32
 GK_SIDE_LEFT, GK_SIDE_RIGHT = 0, 1
 GK_ERR_ARG, GK_ERR_STATE = -1, -4
 GK_PREC_IDENTITY, GK_PREC_CBPR2, GK_PREC_CHEB = 0, 1, 2
@@ -57,7 +58,8 @@ GK_SR_PCG, GK_SR_BICGSTAB = 0, 1
 COMM_KINDS = {0: None, 1: "rccl", 2: "local-group", 3: "xgmi-device-exchange"}
 # resident-step variants (gk_res_info / gk_res_plan_query)
 RES_VARIANTS = {0: None, 1: "prefetch", 2: "pairs", 3: "pairs+lds", 4: "w-only", 5: "w+column", 6: "blocked"}
-RES_INFO_KEYS = ["variant", "G", "r2", "l2", "pf", "cw", "wo", "nt", "r2e", "l2e", "lds", "nres2", "pipe", "cheb_sten", "wt", "blk"]
+RES_INFO_KEYS = ["variant", "G", "r2", "l2", "pf", "cw", "wo", "nt", "r2e", "l2e", "lds", "nres2", "pipe", "cheb_sten", "wt", "blk",
+                 "carry"]
 
 c_int, c_double, c_ll, c_vp = ctypes.c_int, ctypes.c_double, ctypes.c_longlong, ctypes.c_void_p
 _dp = ctypes.POINTER(ctypes.c_double)

@@ -304,7 +304,8 @@ bool res_plan(gk_ctx *c, ResPlan &p, bool hh = false) {
     const int cap = c->tune_res_r2 > 0 ? c->tune_res_r2 : RES_R2_BIG;
     plan_resident(c->nloc, gmax, cap, c->tune_res_wonly, hh,
                   c->tune_nt > 0 || (c->tune_nt < 0 && c->nt_auto), p, c->tune_res_pc, c->tune_res_blk, c->tune_res_pf,
-                  c->tune_res_pipe);
+                  c->tune_res_pipe, c->tune_res_carry);
+    if (c->nranks > 1) p.carry = 0;  // the carried pass is the single-rank launches' (gk_resident.hip)
     if (p.wo && !hh && c->m + 1 > gk::WO_HMAX) return false;  // its H column: WO_HMAX entries of LDS
     return true;
 }
@@ -1590,6 +1591,7 @@ int gk_set_tuning(gk_ctx *c, int key, int value) {
             break;
         case GK_TUNE_RES_WONLY: c->tune_res_wonly = value < 0 ? -1 : (value != 0); break;
         case GK_TUNE_RES_PIPE: c->tune_res_pipe = value < 0 ? -1 : (value != 0); break;
+        case GK_TUNE_RES_PIPE_CARRY: c->tune_res_carry = value < 0 ? -1 : (value != 0); break;
         case GK_TUNE_HH_FUSE: c->tune_hh_fuse = value != 0; break;
         case GK_TUNE_CHEB_STEN: c->tune_cheb_sten = value != 0; break;
         case GK_TUNE_SPIN_WAIT: c->tune_spin_wait = value != 0; break;

@@ -99,6 +99,7 @@ struct gk_ctx {
     int tune_res = -1;                              // -1 auto, 0 off, 1 on where possible
     int tune_res_r2 = 0;                            // cap of resident double2 per thread (0 = auto)
     int tune_res_pipe = -1;                         // w-only MGS step: pipelined pass (-1: the build's default)
+    int tune_res_carry = -1;                        // ... its ring's head carried across the all-gather (-1: the build's)
     int tune_res_wonly = -1;                        // large slabs: w-only variant (-1: by the byte model)
     int tune_verr_order = 1;                        // v_err diagnostics in the reference's dot order
     int tune_hh_fuse = 1;                           // Householder step: small launches folded into the chains

@@ -368,8 +368,15 @@ __device__ __forceinline__ bool res_pin_fold(const ResArgs &a, double &h, double
 
 // TR: the trace stamps (gk_profile_res_trace) are compiled into the MGS-R launches only
 // (the reflection kernels are at the edge of the register file).
-template <int NW = RWAVES, bool TR = false, int SLEEP = RES_POLL_SLEEP>
-__device__ __forceinline__ void res_exchange(const ResArgs &a, int p, const double *sm, double *bc, int *okf) {
+// published(): called by the whole wave right after the publish store and before the first
+// poll, so whatever it issues stays off the path to the workgroup's own granule (the carried
+// pass of k_mgs_wres issues the next pass's first column loads there); nothing by default.
+struct ResNoHook {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <int NW = RWAVES, bool TR = false, int SLEEP = RES_POLL_SLEEP, class HOOK = ResNoHook>
+__device__ __forceinline__ void res_exchange(const ResArgs &a, int p, const double *sm, double *bc, int *okf,
+                                             HOOK &&published = HOOK{}) {
     const int lane = threadIdx.x;
     const int G = gridDim.x;
     const unsigned tag = a.tag0 + (unsigned)p;
@@ -390,6 +397,7 @@ __device__ __forceinline__ void res_exchange(const ResArgs &a, int p, const doub
                            ((u64)tag << 32) | (half ? (unsigned)(bits >> 32) : (unsigned)bits), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     }
+    published();
     const u64 deadline = wall_clock64() + a.timeout;
     double acc = 0.0;
     bool all_ok = true;

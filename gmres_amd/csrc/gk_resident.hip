@@ -308,6 +308,20 @@ __global__ __launch_bounds__(RT, 2) void k_mgs_res(ResArgs a) {
 // streamed; chosen by launch_wres): the pass keeps 14-16 column loads in flight through a
 // ring of WBT buffer pairs with counted waits instead of draining each batch of 16
 // (4096^2: pass 32.65 -> 31.16 us per projection, 251.8 -> 261.8 it/s).
+// CARRY (> 0: the pipelined pass on a single rank, chosen by launch_wres): the ring lives at
+// kernel scope and the two loads of chunks 0 .. CARRY-1 of pass p + 1 -- their addresses do
+// not depend on the dot being gathered -- go out inside pass p's all-gather (head()): wave 0
+// right after it has published the workgroup's granule, waves 1..3 after the barrier and
+// ahead of their touches, which start CARRY chunks later (those chunks go straight to
+// registers).  Pass 0's head goes out before the projection loop; after the last pass the
+// head is issued on clamped columns and retired unused (no branch around a load).  The
+// wait that closes every all-gather drains the head with the touches, so the pass issues
+// chunks CARRY .. WBT-1 at entry and its counted waits hold unchanged; arithmetic and order
+// are the pipelined pass's, results bit-identical.  Not on N ranks: there the rank-total
+// pushers drain vmcnt before they publish, which would put the carried loads on every
+// rank's critical path -- those launches keep CARRY = 0.  The ring registers are live
+// across res_exchange and the loop back-edge: tools/asm_inflight_audit.py checks in the
+// compiler's assembly that nothing names one between its load and the wait.
 // --------------------------------------------------------------------------
 constexpr int WT = 256;  // threads per workgroup (4 waves, one per SIMD)
 #ifndef GK_RES_WB
@@ -386,6 +400,26 @@ constexpr int TOUCH_PACE_HH = GK_RES_TOUCH_PACE_HH;
 #define GK_RES_PIPE_D 8
 #endif
 constexpr int PIPE_D = GK_RES_PIPE_D;
+// Chunks of the pipelined pass's ring carried across the all-gather (k_mgs_wres<.., PIPE, CARRY>):
+// the first PIPE_CARRY chunk pairs of pass p + 1 are loaded inside pass p's all-gather, into
+// ring registers that are otherwise empty for the whole wait.  0 = no such instantiation.
+// 7 builds with 256 VGPRs + 256 AGPRs and no scratch, 8 spills.  A/B at 4096^2, builds
+// interleaved on one box, three runs each (profiles/r08/ab_carry_r08.jsonl): parent / 4 / 5 / 6
+// -> 259.4-260.0 / 264.9-265.6 / 265.8-267.8 / 267.5-268.7 it/s, on another box parent / 6 / 7 ->
+// 262.9-263.4 / 271.9-273.2 / 273.5-275.1; pass 31.1 -> 29.3 us and wait 7.2 -> 7.45 us per
+// projection at 7.  The same build with GK_TUNE_RES_PIPE_CARRY 0: 263.4.
+#ifndef GK_RES_PIPE_CARRY
+#define GK_RES_PIPE_CARRY 7
+#endif
+constexpr int PIPE_CARRY = GK_RES_PIPE_CARRY;
+static_assert(PIPE_CARRY >= 0 && PIPE_CARRY <= PIPE_D, "GK_RES_PIPE_CARRY: 0 .. GK_RES_PIPE_D chunks of the ring");
+// ... and the touch depth of those launches (the touches start at the first chunk that is
+// not carried): 12 / 16 / 20 / 24 with 6 chunks carried -> 266.6-267.3 / 267.1-269.0 /
+// 267.5-268.7 / 267.0-268.7 it/s (same file; 24 lengthens the wait 7.85 -> 8.44 us)
+#ifndef GK_RES_TOUCH_MGS_CARRY
+#define GK_RES_TOUCH_MGS_CARRY 20
+#endif
+constexpr int TOUCH_MGS_CARRY = GK_RES_TOUCH_MGS_CARRY;
 
 // f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>) in order: a loop
 // unrolled by construction, its index a constant in the body
@@ -398,8 +432,10 @@ __device__ __forceinline__ void seq_for(F &&f) {
     seq_apply(f, std::make_integer_sequence<int, N>{});
 }
 
-template <int RW, int LW, int MODE, int WBT = WB, bool PIPE = false>
+template <int RW, int LW, int MODE, int WBT = WB, bool PIPE = false, int CARRY = 0>
 __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
+    static_assert(CARRY >= 0 && CARRY <= WBT && (CARRY == 0 || (PIPE && MODE == RES_MGS && CARRY <= RW)),
+                  "carried chunks: a head of the pipelined pass's ring, register chunks of the MGS step");
     extern __shared__ double2 lw[];  // [LW][WT]
     __shared__ double sm[WT / 64];
     __shared__ double bc[1];
@@ -411,7 +447,8 @@ __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
     const int t = threadIdx.x;
     constexpr int mode = MODE;
     constexpr int PACE = MODE == RES_MGS ? TOUCH_PACE : TOUCH_PACE_HH;
-    constexpr int TCH = MODE == RES_MGS ? (PIPE ? TOUCH_MGS_PIPE : TOUCH_MGS) : TOUCH;  // touched chunks per workgroup
+    // touched chunks per workgroup
+    constexpr int TCH = MODE == RES_MGS ? (PIPE ? (CARRY > 0 ? TOUCH_MGS_CARRY : TOUCH_MGS_PIPE) : TOUCH_MGS) : TOUCH;
     const int j = a.j, np = res_np(mode, j);
     const i64 n2 = a.n >> 1, ld2 = a.ld >> 1;
     const i64 nch = a.nres2 / WT;
@@ -427,6 +464,9 @@ __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
     const i64 sstride = (i64)gridDim.x * WT;
     const i64 sbase = a.nres2 + (i64)res_stream_wg() * WT + t;
     double2 wr[RW];
+    // CARRY: the pipelined pass's ring lives here, not in the pass: slots 0 .. CARRY-1 are
+    // loaded outside it (head, below) and stay in flight across the all-gather
+    [[maybe_unused]] d2v ra[CARRY > 0 ? WBT : 1], rb[CARRY > 0 ? WBT : 1];
     if (mode == RES_HH_DOWN && a.unit_init) {
         // w = e_u built in place (gmres_hh.f90:257-264): no k_set_unit launch, no read
         // of w; the streamed part is written by the thread that streams it later
@@ -487,7 +527,13 @@ __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
             constexpr int D = WBT, NCH = RW + LW;
             static_assert(MODE == RES_MGS && NCH > D && 2 * (D - 1) <= 63,
                           "pipelined pass: the MGS step, counts within vmcnt's 6 bits, V_q default policy");
-            d2v pa[D], pb[D];
+            [[maybe_unused]] d2v pl[CARRY > 0 ? 1 : D], ql[CARRY > 0 ? 1 : D];
+            auto &pa = *[&]() {
+                if constexpr (CARRY > 0) return &ra; else return &pl;
+            }();
+            auto &pb = *[&]() {
+                if constexpr (CARRY > 0) return &rb; else return &ql;
+            }();
             const unsigned lo = (unsigned)t * (unsigned)sizeof(double2);
             // the columns at the workgroup's register and LDS chunk ranges
             const double2 *Ar = A2 + c0 * WT, *Al = A2 + l0 * WT, *Br = B2 + c0 * WT, *Bl = B2 + l0 * WT;
@@ -532,7 +578,9 @@ __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
                     red(acc, wv, bv, kind, (l0 + kl) * WT + t, false);
                 }
             };
-            seq_for<D>(issue);
+            // (CARRY: chunks 0 .. CARRY-1 were issued by head() and have landed -- the wait that
+            // closes every all-gather drains them -- so the counted waits below hold as they are)
+            seq_for<D - CARRY>([&](auto kc) { issue(std::integral_constant<int, decltype(kc)::value + CARRY>{}); });
             seq_for<NCH>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
                 wait(kc);
@@ -619,23 +667,70 @@ __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
         }
         return acc;
     };
+    // CARRY: the two column loads of chunks 0 .. CARRY-1 of pass pn into ring slots 0 .. CARRY-1,
+    // the pass's own statements (V_i non-temporal, V_q default policy, or the re-read of V_i's
+    // first chunk where the pass closes with the norm).  pn = np (after the last pass): the
+    // clamped columns of pass np - 1, valid addresses, retired unused -- no branch around a load.
+    [[maybe_unused]] auto head = [&](int pn) {
+        int zero = 0;  // (the chunk origin opaque per issue site, as in a pass)
+        asm volatile("" : "+s"(zero));
+        const double2 *Ar = V2 + (i64)res_col(mode, j, pn) * ld2 + (wc0 + zero) * WT;
+        const double2 *Br = V2 + (i64)res_col(mode, j, pn + 1) * ld2 + (wc0 + zero) * WT;
+        const bool dot = pn < np - 1;
+        const unsigned lo = (unsigned)t * (unsigned)sizeof(double2);
+        seq_for<CARRY>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            const double2 *ap = Ar + k * WT;
+            const double2 *bp = dot ? Br + k * WT : Ar;
+            d2v &da = ra[k], &db = rb[k];
+            const unsigned off = lo;  // (named outside the asm operands: captured by the generic lambda)
+            asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "=v"(da) : "v"(off), "s"(ap));
+            asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(db) : "v"(off), "s"(bp));
+        });
+    };
+    // ... and the point from which the carried slots hold their data: everything in flight
+    // has landed, and nothing that reads a slot can be placed above it
+    [[maybe_unused]] auto head_landed = [&]() {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        seq_for<CARRY>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            d2v &da = ra[k], &db = rb[k];
+            asm volatile("" : "+v"(da), "+v"(db));
+        });
+    };
     // all-gather of the partials: the same h in every workgroup (and rank)
+    // (CARRY: pass head_p's first chunks go out inside it -- wave 0 once its granule is
+    // published, waves 1..3 ahead of their touches, which then start CARRY chunks later)
     int xi = 0;
-    auto reduce = [&](double acc, double &h, int touch_col) -> bool {
+    auto reduce = [&](double acc, double &h, int touch_col, [[maybe_unused]] int head_p = 0) -> bool {
         clk.passed(a.stamps);
         acc = wave_sum(acc);
         if ((t & 63) == 0) sm[t >> 6] = acc;
         if (PACE > 0 && t == 0) xdone = 0;
         __syncthreads();
+        // (CARRY: each arm has its own head issue into the same ring registers.  A wave runs one
+        // arm only -- t < 64 holds for whole waves -- but the compiler lays them out as two
+        // masked blocks in a row; the comment each arm opens with tells
+        // tools/asm_inflight_audit.py, which reads the assembly, that no wave runs both.)
         if (t < 64) {
-            res_exchange<WT / 64, MODE == RES_MGS, RES_POLL_SLEEP>(a, xi, sm, bc, &okf);
+            if constexpr (CARRY > 0) {
+                asm volatile("; gk-audit: arm wave0");
+                res_exchange<WT / 64, MODE == RES_MGS, RES_POLL_SLEEP>(a, xi, sm, bc, &okf, [&]() { head(head_p); });
+            } else {
+                res_exchange<WT / 64, MODE == RES_MGS, RES_POLL_SLEEP>(a, xi, sm, bc, &okf);
+            }
             if (PACE > 0 && t == 0) *(volatile int *)&xdone = 1;
-        } else if constexpr (TCH > 0) {
-            if (touch_col >= 0) {
+        } else {
+            if constexpr (CARRY > 0) {
+                asm volatile("; gk-audit: arm waves123");
+                head(head_p);
+            }
+            if (TCH > 0 && touch_col >= 0) {
                 // lines [0, 32*TCH) of the workgroup's register-resident part of
-                // the column (contiguous from chunk c0); all loads land in one sink
+                // the column (contiguous from chunk c0, CARRY: from the first chunk that
+                // is not carried); all loads land in one sink
                 // register, drained below before anything can reuse it
-                const i64 r0 = c0, r1 = cend;
+                const i64 r0 = c0 + CARRY, r1 = cend;
                 const i64 lines = (i64)32 * (r1 - r0 < TCH ? (r1 - r0 > 0 ? r1 - r0 : 0) : TCH);
                 const char *base = reinterpret_cast<const char *>(V2 + (i64)touch_col * ld2 + r0 * WT);
                 for (i64 l = t - 64; l < lines; l += WT - 64) {
@@ -649,7 +744,9 @@ __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
             }
         }
         __syncthreads();
+        if constexpr (CARRY > 0) asm volatile("; gk-audit: arms end");
         if constexpr (TCH > 0) asm volatile("s_waitcnt vmcnt(0)" : : "v"(touch_sink) : "memory");
+        if constexpr (CARRY > 0) head_landed();
         ++xi;
         h = bc[0];
         clk.waited(a.stamps);
@@ -685,13 +782,17 @@ __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
         __syncthreads();
         ok = res_pin_fold(a, h, bc, &okf);
     }
+    if constexpr (CARRY > 0) {  // pass 0's head (every later one goes out in the all-gather before it)
+        head(0);
+        head_landed();
+    }
     for (int p = 0; p < np && ok; ++p) {
         const int i = res_col(mode, j, p);
         const int kind = kind_of(p);
         if (mode == RES_MGS && blockIdx.x == 0 && t == 0) hsh[i] = (p < j ? 0.0 : hsh[i]) + h;  // H(i,j) (+)= h
         const double acc = pass(mode == RES_MGS ? h : a.coef * h, i, res_col(mode, j, p + 1), kind);
         if (kind != RK_NONE)
-            ok = reduce(acc, h, p + 1 < np && kind_of(p + 1) == RK_DOT ? res_col(mode, j, p + 2) : -1);
+            ok = reduce(acc, h, p + 1 < np && kind_of(p + 1) == RK_DOT ? res_col(mode, j, p + 2) : -1, p + 1);
     }
     if (!ok) return;  // uniform per workgroup; *err is set
     const bool close = mode == RES_HH_UP && a.close_hh;
@@ -1153,7 +1254,7 @@ static bool wonly_pays(i64 n2, int G) { return wonly_bytes(n2, G) < pairs_bytes(
 //   else w and the running column in 2 x 12 registers, plus
 //   w of 18 more chunks per workgroup in LDS, the rest streamed.
 void plan_resident(i64 nloc, int gmax, int cap, int tune_wonly, bool hh, bool nt, ResPlan &p,
-                   int tune_pc, int tune_blk, int tune_pf, int tune_pipe) {
+                   int tune_pc, int tune_blk, int tune_pf, int tune_pipe, int tune_carry) {
     const i64 n2 = nloc / 2;
     const i64 dcw = gk::RT - 64;
     // small vectors: no more workgroups than two chunks each (a cheaper all-gather)
@@ -1237,6 +1338,9 @@ void plan_resident(i64 nloc, int gmax, int cap, int tune_wonly, bool hh, bool nt
         // RES_RW + RES_LW whole chunks, nothing is streamed and there is no odd element.
         p.pipe = RES_PIPE_OK && !hh && (tune_pipe < 0 ? RES_PIPE : tune_pipe != 0) && p.r2e == RES_RW &&
                  p.l2e == RES_LW && nloc % 2 == 0 && n2 == (i64)p.G * (RES_RW + RES_LW) * gk::WT && p.nres2 == n2;
+        // ... with the head of its ring carried across the all-gather (single-rank launches:
+        // res_plan clears it on N ranks)
+        p.carry = p.pipe && (tune_carry < 0 || tune_carry != 0) ? gk::PIPE_CARRY : 0;
         return;
     } else {
         p.G = gmax;
@@ -1275,6 +1379,7 @@ void plan_info(const ResPlan &p, bool on, long long *info) {
     info[RPI_NRES2] = p.nres2;
     info[RPI_WT] = p.wt;
     info[RPI_PIPE] = p.pipe;
+    info[RPI_CARRY] = p.carry;
 }
 
 // -------------------------------------------------------------- launchers ---
@@ -1324,15 +1429,16 @@ int launch_res_t(const ResPlan &p, const ResArgs &a, int dev, hipStream_t st, st
     }
 }
 
-template <int MODE, bool PIPE = false>
+template <int MODE, bool PIPE = false, int CARRY = 0>
 int launch_wres_m(const ResPlan &p, const ResArgs &a, int dev, hipStream_t st, std::string &msg) {
     constexpr int RW = MODE == RES_MGS ? RES_RW : RES_RW_HH;
     constexpr int LW = MODE == RES_MGS ? RES_LW : RES_LW_HH;
     constexpr int WBT = PIPE ? PIPE_D : (MODE == RES_MGS ? WB : WB_HH);
     static std::atomic<int> attr[ATTR_DEVS];
-    const int e = dyn_lds(reinterpret_cast<const void *>(&k_mgs_wres<RW, LW, MODE, WBT, PIPE>), dev, p.lds, attr, msg);
+    const int e =
+        dyn_lds(reinterpret_cast<const void *>(&k_mgs_wres<RW, LW, MODE, WBT, PIPE, CARRY>), dev, p.lds, attr, msg);
     if (e != GK_OK) return e;
-    k_mgs_wres<RW, LW, MODE, WBT, PIPE><<<p.G, WT, p.lds, st>>>(a);
+    k_mgs_wres<RW, LW, MODE, WBT, PIPE, CARRY><<<p.G, WT, p.lds, st>>>(a);
     return launched(msg);
 }
 
@@ -1347,6 +1453,15 @@ int launch_wres(const ResPlan &p, const ResArgs &a, int dev, hipStream_t st, std
                     if (p.r2e != RES_RW || p.l2e != RES_LW || (a.n & 1) || a.nres2 != a.n / 2)
                         return fail(msg, GK_ERR_STATE, "pipelined w-only step on a plan that is not full (%d + %d chunks)",
                                     p.r2e, p.l2e);
+                    if constexpr (PIPE_CARRY > 0) {
+                        // (N ranks: the pushers drain vmcnt before they publish, which would put
+                        // the carried loads on every rank's critical path)
+                        if (p.carry != 0) {
+                            if (a.nranks != 1 || p.carry != PIPE_CARRY)
+                                return fail(msg, GK_ERR_STATE, "carried pass (%d chunks) on %d ranks", p.carry, a.nranks);
+                            return launch_wres_m<RES_MGS, true, PIPE_CARRY>(p, a, dev, st, msg);
+                        }
+                    }
                     return launch_wres_m<RES_MGS, true>(p, a, dev, st, msg);
                 }
             }

@@ -23,6 +23,7 @@ struct ResPlan {
     int bvar = -1;         // ... its instantiation (gk::BLK_*)
     int wt = 0;            // threads per workgroup = double2 per chunk (set by plan_resident)
     bool pipe = false;     // w-only MGS step: the software-pipelined pass (full workgroups only)
+    int carry = 0;         // ... chunks of its ring carried across each all-gather (single rank only)
     i64 nres2 = 0;
     int lds = 0;
 };
@@ -35,12 +36,13 @@ GK_HIDDEN i64 wonly_bytes(i64 n2, int G);
 
 // The variant a slab of nloc local unknowns runs on, from the tuning values alone.
 GK_HIDDEN void plan_resident(i64 nloc, int gmax, int cap, int tune_wonly, bool hh, bool nt, ResPlan &p,
-                             int tune_pc = -1, int tune_blk = 1, int tune_pf = 0, int tune_pipe = -1);
+                             int tune_pc = -1, int tune_blk = 1, int tune_pf = 0, int tune_pipe = -1,
+                             int tune_carry = -1);
 GK_HIDDEN bool nt_auto_for(i64 max_nloc);
 
 // gk_res_plan_query / gk_res_info layout
 enum { RPI_VARIANT = 0, RPI_G, RPI_R2, RPI_L2, RPI_PF, RPI_CW, RPI_WO, RPI_NT, RPI_R2E, RPI_L2E, RPI_LDS, RPI_NRES2, RPI_PIPE,
-       RPI_CHEB_STEN, RPI_WT, RPI_BLK };
+       RPI_CHEB_STEN, RPI_WT, RPI_BLK, RPI_CARRY };
 GK_HIDDEN void plan_info(const ResPlan &p, bool on, long long *info);
 
 // Launch plan p's kernel for a.mode on stream st of device dev.  Returns GK_OK, or a

@@ -362,8 +362,9 @@ int gk_sync(gk_ctx *ctx);
  * whether the w-only MGS step runs its software-pipelined pass (GK_TUNE_RES_PIPE; 1 / 0),
  * (gk_res_info only) whether the Arnoldi step's Chebyshev(k) pass forms z = A v in its own
  * stage 0 (1 / 0; -1 on a multi-rank context whose smallest slab is not known
- * until its first solve), the threads per workgroup (= double2 per chunk), and the
- * projection block S (1: strict MGS-R).
+ * until its first solve), the threads per workgroup (= double2 per chunk), the
+ * projection block S (1: strict MGS-R), and `carry`: the chunks of the pipelined pass's ring
+ * that the launches load across each all-gather (GK_TUNE_RES_PIPE_CARRY; 0: none).
  * gk_res_plan_query: pure host computation for a slab of nloc unknowns on a
  * device with `cus` compute units shared by `share` contexts; hh != 0 the
  * reflection chains' plan; nt: -1 auto (from nloc), 0 / 1 forced; block: the
@@ -378,7 +379,7 @@ int gk_sync(gk_ctx *ctx);
 #define GK_RES_WONLY 4
 #define GK_RES_WCOL 5
 #define GK_RES_BLOCKED 6
-#define GK_RES_INFO_LEN 16
+#define GK_RES_INFO_LEN 17
 int gk_res_plan_query(long long nloc, int cus, int share, int hh, int nt, int block, long long *info);
 int gk_res_info(gk_ctx *ctx, int hh, long long *info);
 
@@ -419,6 +420,16 @@ int gk_res_info(gk_ctx *ctx, int hh, long long *info);
  *                          It runs only where every workgroup holds its full 89 + 39 chunks and
  *                          nothing is streamed (4096^2 on 256 CUs); gk_res_info reports whether
  *                          the launches run it (`pipe`)
+ *   GK_TUNE_RES_PIPE_CARRY the pipelined pass with the head of its ring carried across the
+ *                          all-gather: the first GK_RES_PIPE_CARRY chunk pairs of the next pass are
+ *                          loaded while the workgroup waits for the dot (the ring registers are
+ *                          otherwise empty there), and the L2 touches start that many chunks
+ *                          later; bit-identical results.  -1 (default) the build's choice
+ *                          (GK_RES_PIPE_CARRY chunks; 0 = not built), 0 off, anything else on.
+ *                          Only where the pipelined pass runs and only on a single rank (on N
+ *                          ranks the pushers drain their loads before they publish, so carried
+ *                          loads would sit on every rank's critical path: those launches keep the
+ *                          plain pipelined pass); gk_res_info reports the chunks carried (`carry`)
  *   GK_TUNE_VERR_ORDER     1 (default): the v_err diagnostics (gk_mgs_verr, gk_hh_verr) use the
  *                          reference's dot_product order, one running sum per dot (bit-identical
  *                          to the reference's formula on the same basis; single rank); 0: tree
@@ -523,6 +534,7 @@ int gk_res_info(gk_ctx *ctx, int hh, long long *info);
 #define GK_TUNE_SR_TWO_LEVEL 29
 #define GK_TUNE_RES_PIPE 30
 #define GK_TUNE_RIGHT_FUSED 31
+#define GK_TUNE_RES_PIPE_CARRY 32
 int gk_set_tuning(gk_ctx *ctx, int key, int value);
 /* Test hook: hold = 1 enqueues on the context's stream a wait for a mapped host
  * word that only hold = 0 writes (hipStreamWaitValue32) -- every later kernel of
