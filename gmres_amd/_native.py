@@ -45,6 +45,7 @@ GK_TUNE_RES_PIPE = 30
 GK_TUNE_RIGHT_FUSED = 31
 GK_TUNE_RES_PIPE_CARRY = 32
 GK_SIDE_LEFT, GK_SIDE_RIGHT = 0, 1
+GK_BASIS_F64, GK_BASIS_F32 = 0, 1
 GK_ERR_ARG, GK_ERR_STATE = -1, -4
 GK_PREC_IDENTITY, GK_PREC_CBPR2, GK_PREC_CHEB = 0, 1, 2
 (GK_KID_PROJ, GK_KID_STENCIL, GK_KID_SCALE, GK_KID_UPDATE, GK_KID_COMM, GK_KID_OTHER, GK_KID_RES, GK_KID_PREC,
@@ -57,9 +58,13 @@ KID_NAMES = ["proj", "stencil", "scale", "update", "comm", "other", "res", "prec
 GK_SR_PCG, GK_SR_BICGSTAB = 0, 1
 COMM_KINDS = {0: None, 1: "rccl", 2: "local-group", 3: "xgmi-device-exchange"}
 # resident-step variants (gk_res_info / gk_res_plan_query)
-RES_VARIANTS = {0: None, 1: "prefetch", 2: "pairs", 3: "pairs+lds", 4: "w-only", 5: "w+column", 6: "blocked"}
+GK_RES_CB = 7
+RES_VARIANTS = {0: None, 1: "prefetch", 2: "pairs", 3: "pairs+lds", 4: "w-only", 5: "w+column", 6: "blocked",
+                GK_RES_CB: "compressed-basis"}
 RES_INFO_KEYS = ["variant", "G", "r2", "l2", "pf", "cw", "wo", "nt", "r2e", "l2e", "lds", "nres2", "pipe", "cheb_sten", "wt", "blk",
                  "carry"]
+# gk_cb_plan_query (the compressed-basis step's planner)
+CB_INFO_KEYS = ["G", "rw", "lw", "r2e", "l2e", "lds", "nres2", "nstream2", "on", "lds_static"]
 
 c_int, c_double, c_ll, c_vp = ctypes.c_int, ctypes.c_double, ctypes.c_longlong, ctypes.c_void_p
 _dp = ctypes.POINTER(ctypes.c_double)
@@ -102,6 +107,9 @@ _SIGS = {
     "gk_xchg_selftest": (c_int, [c_vp, c_int]),
     "gk_set_precond": (c_int, [c_vp, c_int, _dp, c_int, c_int]),
     "gk_set_precond_side": (c_int, [c_vp, c_int]),
+    "gk_set_basis_precision": (c_int, [c_vp, c_int]),
+    "gk_get_basis_precision": (c_int, [c_vp, _ip]),
+    "gk_cb_plan_query": (c_int, [c_ll, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
     "gk_set_rhs": (c_int, [c_vp, _dp]),
     "gk_set_rhs_ones": (c_int, [c_vp]),
     "gk_rhs_norm": (c_int, [c_vp, _dp]),

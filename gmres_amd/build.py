@@ -28,20 +28,23 @@ DRIVER = os.path.join(LIB, "test_mfp_hip")
 
 # Translation units compiled in parallel, one per subsystem: the C-ABI and the
 # streaming kernels (gk_api), the Chebyshev pass split by level count, the blocked
-# and the strict resident steps (gk_blk, gk_resident), the collectives (gk_comm)
-# and the short-recurrence solvers (gk_sr_api).  Seconds per unit, one compile at
-# a time on an 8-core build machine: gk_api 7, gk_cheb0..3 26-31, gk_blk 15,
-# gk_resident 42-48 (the unrolled resident kernels), gk_comm 4, gk_sr_api 8; the
-# single gk_api unit they were split from took 47-60.
+# and the strict resident steps (gk_blk, gk_resident), the collectives (gk_comm),
+# the short-recurrence solvers (gk_sr_api) and the compressed-basis step (gk_cb).
+# Seconds per unit, one compile at a time on an 8-core build machine: gk_api 7,
+# gk_cheb0..3 26-31, gk_blk 15, gk_resident 42-48 (the unrolled resident kernels),
+# gk_comm 4, gk_sr_api 8; the single gk_api unit they were split from took 47-60.
 HIP_SOURCES = [os.path.join(CSRC, f) for f in ("gk_api.hip", "gk_cheb.hip", "gk_blk.hip", "gk_resident.hip",
-                                                "gk_comm.hip", "gk_sr_api.hip")]
+                                                "gk_comm.hip", "gk_sr_api.hip", "gk_cb.hip")]
 # (source, extra defines, object name): the Chebyshev pass in GK_CF_PARTS parts
 GK_CF_PARTS = 4
 HIP_UNITS = ([(HIP_SOURCES[0], [], "gk_api.o")] + [(HIP_SOURCES[1], [f"GK_CF_PART={p}"], f"gk_cheb{p}.o")
                                                     for p in range(GK_CF_PARTS)]
-             + [(s, [], os.path.basename(s)[:-4] + ".o") for s in HIP_SOURCES[2:]])
+             + [(s, [], os.path.basename(s)[:-4] + ".o") for s in HIP_SOURCES[2:6]])
+# ... and the unit of the opt-in FP32-compressed basis (HIP_UNITS stays the FP64 solvers' list)
+HIP_UNITS_CB = [(HIP_SOURCES[6], [], "gk_cb.o")]
 HIP_HEADERS = [os.path.join(CSRC, h) for h in ("gk_common.hpp", "gk_kernels.hpp", "gk_cheb.hpp", "gk_res.hpp",
-                                                "gk_blk.hpp", "gk_sr.hpp", "gk_host.hpp", "gk_resident.hpp")]
+                                                "gk_blk.hpp", "gk_sr.hpp", "gk_host.hpp", "gk_resident.hpp",
+                                                "gk_cb.hpp")]
 HIP_DEPS = HIP_SOURCES + HIP_HEADERS + [os.path.join(ROOT, "include", "gmres_hip.h")]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall"]
 F_SOURCES = [os.path.join(FSRC, "gmres_hip.f90")]
@@ -94,7 +97,7 @@ def _compile_link(so: str, defines: list[str]) -> None:
     pass at run time; a spilled resident kernel holds w in scratch memory): the
     build fails here, naming them."""
     objs, procs = [], []
-    for src, unit_defs, oname in HIP_UNITS:
+    for src, unit_defs, oname in HIP_UNITS + HIP_UNITS_CB:
         obj = os.path.join(os.path.dirname(so), oname)
         cmd = [hipcc(), *HIP_FLAGS, *[f"-D{x}" for x in defines + unit_defs], "-c", src, "-o", obj,
                "-Rpass-analysis=kernel-resource-usage"]
@@ -105,7 +108,8 @@ def _compile_link(so: str, defines: list[str]) -> None:
     for p in procs:
         err = p.communicate()[1]
         sys.stderr.write("".join(l + "\n" for l in err.splitlines() if "warning:" in l or "error" in l))
-        for name in ("k_cheb_fused", "k_mgs_wpc", "k_mgs_wres", "k_mgs_res", "k_mgs_blk", "k_right_cbpr2"):
+        for name in ("k_cheb_fused", "k_mgs_wpc", "k_mgs_wres", "k_mgs_res", "k_mgs_blk", "k_right_cbpr2",
+                     "k_mgs_wcb"):
             bad += _scratch_kernels(err, name)
     if any(p.returncode for p in procs):
         raise subprocess.CalledProcessError(max(p.returncode for p in procs), "hipcc")

@@ -21,6 +21,7 @@
 #include <cstring>
 
 #include "gk_blk.hpp"
+#include "gk_cb.hpp"
 #include "gk_host.hpp"
 #include "gk_kernels.hpp"
 #include "gk_resident.hpp"
@@ -385,6 +386,54 @@ int res_step(gk_ctx *c, int j, const ResPlan &p, const double *pin, int npin, do
     return e == GK_OK ? GK_OK : set_err(e, "%s", msg.c_str());
 }
 
+// Compressed basis (gk_set_basis_precision GK_BASIS_F32): can step j run as one resident
+// launch of k_mgs_wcb?  Single rank by construction; the blocked / prefetching steps do
+// not exist on float columns (GK_TUNE_RES_BLOCK, GK_TUNE_RES_PF ignored).
+bool cb_plan_ctx(gk_ctx *c, gk::CbPlan &p) {
+    if (c->tune_res == 0 || c->res_broken || c->res_cus <= 0 || c->res_gath == nullptr || c->nranks > 1) return false;
+    if (c->tune_res < 0 && c->res_share > 1) return false;  // (as res_plan: auto assumes one context per device)
+    gk::plan_cb(c->nloc, c->res_cus, c->res_share, c->m, p);
+    return p.on;
+}
+
+// The resident launch of step j on float columns: res_step's RES_MGS arguments.
+int cb_step(gk_ctx *c, int j, const gk::CbPlan &p, const double *pin, int npin, double *hs, double *hcopy) {
+    ProfScope ps(c, GK_KID_RES);
+    const int np = 2 * j;
+    if (c->res_tag > 0xF0000000u) {  // tags must never repeat within the granule region's lifetime
+        HIPCHK(hipMemsetAsync(c->res_gath, 0, sizeof(gk::u64) * gk::RES_GATH_ALL, c->st));
+        c->res_tag = 1;
+    }
+    gk::ResArgs a{};
+    a.w = c->w;
+    a.mode = gk::RES_MGS;
+    a.coef = 1.0;
+    a.ld = c->ld;
+    a.pin = pin;
+    a.npin = npin;
+    a.hs = hs;
+    a.hcopy = hcopy;
+    a.gath = c->res_gath;
+    a.j = j;
+    a.n = c->nloc;
+    a.nres2 = p.nres2;
+    a.r2e = p.r2e;
+    a.l2e = p.l2e;
+    a.tag0 = c->res_tag;
+    c->res_tag += (unsigned)np;
+    a.timeout = (gk::u64)c->res_timeout_ms * (gk::u64)c->xs_tick_per_ms;
+    a.err = c->res_err_dev;
+    a.stamps = c->res_split ? c->res_stamps : nullptr;
+    if (c->res_trace != nullptr && j == c->res_trace_j && c->res_trace_mode == gk::RES_MGS) {
+        a.trace = c->res_trace;
+        c->res_trace_g = p.G;
+        c->res_trace_np = np;
+    }
+    a.nranks = 1;
+    std::string msg;
+    const int e = gk::cb_launch(p, a, cb_base(c), cb_vjw(c), c->dev, c->st, msg);
+    return e == GK_OK ? GK_OK : set_err(e, "%s", msg.c_str());
+}
 
 int d2h_sync(gk_ctx *c, double *host, const double *dev, int count) {
     HIPCHK(hipMemcpyAsync(c->hcol_host, dev, sizeof(double) * count, hipMemcpyDeviceToHost, c->st));
@@ -720,7 +769,13 @@ int gram(gk_ctx *c, const double *base, int ncols, std::vector<double> &G) {
         for (int aa = 0; aa <= bb; ++aa) pr.push_back(make_short2((short)aa, (short)bb));
     const int np = (int)pr.size();
     HIPCHK(hipMemcpyAsync(c->gram_pairs, pr.data(), sizeof(short2) * np, hipMemcpyHostToDevice, c->st));
-    if (verr_ref_order(c)) {  // one running sum per pair, k in order (the reference's dot_product)
+    if (cb_on(c) && base == c->V) {  // float columns: the tree (no reference to match in its order)
+        ProfScope ps(c, GK_KID_OTHER);
+        HIPCHK(gk::cb_gram(c->gram_nblk, cb_base(c), c->ld, ncols, c->nloc, c->gram_pairs, np, c->gram_slab, c->st));
+        gk::k_gram_reduce<<<(np + gk::TPB - 1) / gk::TPB, gk::TPB, 0, c->st>>>(c->gram_slab, c->gram_nblk,
+                                                                            np, c->gram_out);
+        LAUNCHCHK();
+    } else if (verr_ref_order(c)) {  // one running sum per pair, k in order (the reference's dot_product)
         ProfScope ps(c, GK_KID_OTHER);
         gk::k_seqdot_pairs<<<(np + 63) / 64, 64, 0, c->st>>>(base, c->ld, c->nloc, c->gram_pairs, np, c->gram_out);
         LAUNCHCHK();
@@ -780,7 +835,9 @@ int reflect_chain_down(gk_ctx *c, double *v, int k, i64 unit_g = -1, int flags =
 // (AXPY_i fused with dot_{i+1}), each dot all-reduced, then h = ||w|| and
 // V(:,j+1) = w / h with H(1:j+1, j) published to mapped host memory.
 // gmres_mgsr.f90:341-363, :384.
+int mgs_chain_cb(gk_ctx *c, int j, int np);
 int mgs_chain(gk_ctx *c, int j, int np) {
+    if (cb_on(c)) return mgs_chain_cb(c, j, np);
     const i64 ld = c->ld;
     double *V = c->V;
     const int m2 = c->m + 2;
@@ -804,6 +861,34 @@ int mgs_chain(gk_ctx *c, int j, int np) {
     }
     CHK(allreduce(c, slot(c, s0), np));
     return scale(c, V + (i64)j * ld, c->w, slot(c, s0), np, hs + j, c->hallh_dev + (i64)(j - 1) * m2, hs, j);
+}
+
+// mgs_chain on float columns (gk_cb.hpp): the same launches, slots and H slots, with
+// k_proj_cb / k_scale_cb; the closing writes FP32 column j + 1 and vjw.
+int mgs_chain_cb(gk_ctx *c, int j, int np) {
+    const int m2 = c->m + 2;
+    double *hs = c->hall + (i64)(j - 1) * m2;
+    int s0 = 0, s1 = 1;
+    const int np_total = 2 * j;
+    const bool nt = c->tune_nt > 0 || (c->tune_nt < 0 && c->nt_auto);
+    const bool small = (c->nloc / 2 + (i64)c->np_pj * gk::TPB - 1) / ((i64)c->np_pj * gk::TPB) <= 4;  // (launch_proj)
+    for (int p = 0; p < np_total; ++p) {
+        const int i = p % j;
+        CHK(allreduce(c, slot(c, s0), np));
+        const float *vb = p + 1 < np_total ? cb_col(c, (p + 1) % j) : nullptr;
+        {
+            ProfScope ps(c, GK_KID_PROJ);
+            HIPCHK(gk::cb_proj(c->np_pj, nt, small, c->w, cb_col(c, i), vb, slot(c, s0), np, slot(c, s1), hs + i,
+                               c->nloc, p < j ? 1 : 0, c->st));
+        }
+        np = c->np_pj;
+        std::swap(s0, s1);
+    }
+    CHK(allreduce(c, slot(c, s0), np));
+    ProfScope ps(c, GK_KID_SCALE);
+    HIPCHK(gk::cb_scale(c->nblk_stream, cb_col(c, j), cb_vjw(c), nullptr, c->w, slot(c, s0), np, hs + j, c->nloc,
+                        c->hallh_dev + (i64)(j - 1) * m2, hs, j, c->st));
+    return GK_OK;
 }
 
 // Capture mgs_chain(j) once as a graph (its kernel arguments and communicator
@@ -1043,6 +1128,37 @@ int gk_set_precond_side(gk_ctx *c, int side) {
     return GK_OK;
 }
 
+int gk_set_basis_precision(gk_ctx *c, int prec) {
+    CHK(check_ctx(c));
+    if (prec != GK_BASIS_F64 && prec != GK_BASIS_F32) return set_err(GK_ERR_ARG, "bad basis precision %d", prec);
+    if (prec == GK_BASIS_F32) {
+        if (c->nranks > 1 || c->comm != nullptr || c->lg != nullptr)
+            return set_err(GK_ERR_STATE, "the FP32 basis needs a single-rank context (no communicator)");
+        if (c->m < 3) return set_err(GK_ERR_ARG, "the FP32 basis needs m >= 3 (m = %d)", c->m);
+    }
+    sr_invalidate(c);
+    c->cycle_mgs = c->cycle_hh = false;  // the open cycle's basis is stored in the other format
+    if (prec != c->basis) graph_reset(c);  // the captured steps hold column pointers
+    c->basis = prec;
+    return GK_OK;
+}
+
+int gk_get_basis_precision(gk_ctx *c, int *prec) {
+    CHK(check_ctx(c));
+    if (prec == nullptr) return set_err(GK_ERR_ARG, "null prec");
+    *prec = c->basis;
+    return GK_OK;
+}
+
+int gk_cb_plan_query(long long nloc, int cus, int share, int m, long long *info) {
+    if (info == nullptr || nloc < 2 || cus < 1 || share < 1 || m < 1) return set_err(GK_ERR_ARG, "bad plan query");
+    static_assert(GK_CB_INFO_LEN == gk::CPI_LEN, "gk_cb_plan_query layout");
+    gk::CbPlan p;
+    gk::plan_cb(nloc, cus, share, m, p);
+    gk::cb_plan_info(p, info);
+    return GK_OK;
+}
+
 int gk_set_rhs(gk_ctx *c, const double *b) {
     CHK(check_ctx(c));
     sr_invalidate(c);
@@ -1103,7 +1219,12 @@ int gk_get_basis(gk_ctx *c, int which, int col, double *out) {
     if (base == nullptr) return set_err(GK_ERR_ARG, "basis %d not available", which);
     if (col < 0 || col >= ncol) return set_err(GK_ERR_ARG, "bad column %d", col);
     HIPCHK(hipSetDevice(c->dev));
-    HIPCHK(hipMemcpyAsync(out, base + (i64)col * c->ld, sizeof(double) * c->nloc, hipMemcpyDeviceToHost, c->st));
+    const double *src = base + (i64)col * c->ld;
+    if (which == 0 && cb_on(c)) {  // the stored float column, widened (exact) through aux
+        HIPCHK(gk::cb_widen(c->nblk_stream, c->aux, cb_col(c, col), c->nloc, c->st));
+        src = c->aux;
+    }
+    HIPCHK(hipMemcpyAsync(out, src, sizeof(double) * c->nloc, hipMemcpyDeviceToHost, c->st));
     CHK(sync_st(c));
     return GK_OK;
 }
@@ -1156,7 +1277,13 @@ int gk_mgs_cycle_start(gk_ctx *c, double *beta) {
     else
         CHK(op_precond(c, c->x, c->w, true, gk::ACC_NORM, nullptr, slot(c, 0)));
     CHK(allreduce(c, slot(c, 0), c->last_np));
-    CHK(scale(c, c->V, c->w, slot(c, 0), c->last_np, c->hcol));
+    if (cb_on(c)) {  // FP32 column 1, and widened to v1w (the first dot's partner) and vjw (step 1's input)
+        ProfScope ps(c, GK_KID_SCALE);
+        HIPCHK(gk::cb_scale(c->nblk_stream, cb_col(c, 0), cb_vjw(c), cb_v1w(c), c->w, slot(c, 0), c->last_np, c->hcol,
+                            c->nloc, nullptr, nullptr, 0, c->st));
+    } else {
+        CHK(scale(c, c->V, c->w, slot(c, 0), c->last_np, c->hcol));
+    }
     CHK(d2h_sync(c, beta, c->hcol, 1));
     c->cycle_mgs = true;
     c->cycle_hh = false;
@@ -1175,13 +1302,24 @@ int gk_mgs_step_async(gk_ctx *c, int j) {
     c->prof_on_step = (j % c->prof_every) == 0;
     const int s0 = 0;
     ResPlan rp;
-    const bool res = res_plan(c, rp);
+    gk::CbPlan cp;
+    const bool cb = cb_on(c);
+    const bool res = cb ? cb_plan_ctx(c, cp) : res_plan(c, rp);
+    // the operator's input V(:,j) and the first dot's partner V(:,1); compressed basis: their
+    // widened copies (the operator stage itself is the same launches)
+    const double *vj = cb ? cb_vjw(c) : V + (i64)(j - 1) * ld, *v1 = cb ? cb_v1w(c) : V;
     // w = M^-1 A V(:,j) (side right: A M^-1 V(:,j)), fused with the first dot <w, V(:,1)>
     if (right_prec(c))
-        CHK(op_right(c, V + (i64)(j - 1) * ld, c->w, gk::ACC_DOT, V, slot(c, s0)));
+        CHK(op_right(c, vj, c->w, gk::ACC_DOT, v1, slot(c, s0)));
     else
-        CHK(op_precond(c, V + (i64)(j - 1) * ld, c->w, false, gk::ACC_DOT, V, slot(c, s0)));
+        CHK(op_precond(c, vj, c->w, false, gk::ACC_DOT, v1, slot(c, s0)));
     int np = c->last_np;
+    if (res && cb) {  // ... on float columns (k_mgs_wcb)
+        CHK(cb_step(c, j, cp, slot(c, s0), np, hs, c->hallh_dev + (i64)(j - 1) * m2));
+        HIPCHK(hipEventRecord(c->ev_step[j], c->st));
+        c->prof_on_step = true;
+        return GK_OK;
+    }
     if (res) {  // the whole cascade + norm + scale as one resident launch
         // N ranks on the device exchange: the first dot's rank totals inside the launch
         // (GK_TUNE_RES_FOLD) instead of a k_xchg launch before it
@@ -1259,8 +1397,12 @@ int gk_update_x(gk_ctx *c, const double *y, int n_out) {
     if (right_prec(c)) {  // x += M^-1 (V y): t = V y in w, M^-1 t in z
         {
             ProfScope ps(c, GK_KID_UPDATE);
-            gk::k_update_x<false><<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->w, c->V, c->ld, c->ydev, n_out, c->nloc);
-            LAUNCHCHK();
+            if (cb_on(c)) {
+                HIPCHK(gk::cb_update_x(c->nblk_stream, false, c->w, cb_base(c), c->ld, c->ydev, n_out, c->nloc, c->st));
+            } else {
+                gk::k_update_x<false><<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->w, c->V, c->ld, c->ydev, n_out, c->nloc);
+                LAUNCHCHK();
+            }
         }
         CHK(precond_sweeps(c, c->w, c->z, gk::ACC_NONE, nullptr, nullptr));
         ProfScope ps(c, GK_KID_UPDATE);
@@ -1268,8 +1410,12 @@ int gk_update_x(gk_ctx *c, const double *y, int n_out) {
         LAUNCHCHK();
     } else {
         ProfScope ps(c, GK_KID_UPDATE);
-        gk::k_update_x<true><<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->x, c->V, c->ld, c->ydev, n_out, c->nloc);
-        LAUNCHCHK();
+        if (cb_on(c)) {
+            HIPCHK(gk::cb_update_x(c->nblk_stream, true, c->x, cb_base(c), c->ld, c->ydev, n_out, c->nloc, c->st));
+        } else {
+            gk::k_update_x<true><<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->x, c->V, c->ld, c->ydev, n_out, c->nloc);
+            LAUNCHCHK();
+        }
     }
     CHK(sync_st(c));
     if (c->prof) CHK(prof_harvest(c));
@@ -1322,6 +1468,7 @@ static int hh_pivot(gk_ctx *c, int j, double *hostout, int nout) {
 
 int gk_hh_cycle_start(gk_ctx *c, int precondition, double *g1) {
     CHK(check_ctx(c));
+    if (cb_on(c)) return set_err(GK_ERR_STATE, "the FP32 basis is MGS-R only (gk_set_basis_precision)");
     sr_invalidate(c);
     HIPCHK(hipSetDevice(c->dev));
     if (c->nranks > 1 && c->rank == 0 && c->nloc < c->m + 2)
@@ -1370,6 +1517,7 @@ int gk_hh_cycle_start(gk_ctx *c, int precondition, double *g1) {
 
 int gk_hh_step_async(gk_ctx *c, int j, int precondition) {
     CHK(check_ctx(c));
+    if (cb_on(c)) return set_err(GK_ERR_STATE, "the FP32 basis is MGS-R only (gk_set_basis_precision)");
     if (j < 1 || j > c->m) return set_err(GK_ERR_ARG, "step j=%d outside 1..%d", j, c->m);
     if (!c->cycle_hh) return set_err(GK_ERR_STATE, "gk_hh_step before gk_hh_cycle_start");
     if (precondition && right_prec(c))
@@ -1809,6 +1957,25 @@ int gk_res_info(gk_ctx *c, int hh, long long *info) {
     ResPlan p;
     const bool on = res_plan(c, p, hh != 0);
     plan_info(p, on, info);
+    if (cb_on(c) && hh == 0) {  // the MGS-R step of a compressed-basis context: k_mgs_wcb's plan
+        gk::CbPlan cp;
+        const bool cbon = cb_plan_ctx(c, cp);
+        for (int k = 0; k < GK_RES_INFO_LEN; ++k) info[k] = 0;
+        if (cbon) {
+            info[gk::RPI_VARIANT] = GK_RES_CB;
+            info[gk::RPI_G] = cp.G;
+            info[gk::RPI_R2] = gk::CB_RW;
+            info[gk::RPI_L2] = gk::CB_LW;
+            info[gk::RPI_WO] = 1;
+            info[gk::RPI_NT] = 1;
+            info[gk::RPI_R2E] = cp.r2e;
+            info[gk::RPI_L2E] = cp.l2e;
+            info[gk::RPI_LDS] = cp.lds;
+            info[gk::RPI_NRES2] = cp.nres2;
+            info[gk::RPI_WT] = gk::CB_WT;
+            info[gk::RPI_BLK] = 1;
+        }
+    }
     // op_precond_sten's conditions, without its collective (the smallest slab of
     // a multi-rank context is gathered at its first solve)
     int cs = c->pkind == GK_PREC_CHEB && c->tune_cheb_sten && c->pdeg <= gk::CF_LMAX && c->N >= gk::CF_PTS &&

@@ -65,6 +65,7 @@ struct gk_ctx {
     double p0 = 8.2, p1 = 0.2;
     int side = GK_SIDE_LEFT;   // MGS-R: left (the reference) or right preconditioning (gk_set_precond_side)
     int tune_right_fused = 1;  // side right, cbpr2, one rank: w = A M^-1 v as one march (k_right_cbpr2)
+    int basis = GK_BASIS_F64;  // MGS-R: storage precision of the Krylov columns (gk_set_basis_precision, gk_cb.hpp)
     // decomposition / comm
     int nranks = 1, rank = 0, max_lines = 0;
     int min_lines = 0;  // smallest slab of any rank (0: not gathered yet; ensure_min_lines)
@@ -205,6 +206,14 @@ int fill_hash(gk_ctx *c, double *x, unsigned long long seed);  // k_fill_hash of
 inline void sr_invalidate(gk_ctx *c) { c->sr_solver = -1; }
 // Householder GMRES and the short-recurrence solvers precondition on the left only.
 inline bool right_prec(const gk_ctx *c) { return c->side == GK_SIDE_RIGHT && c->pkind != GK_PREC_IDENTITY; }
+
+// Compressed basis (gk_cb.hpp): the FP32 columns in the lower half of V, the two widened
+// FP64 vectors the operator stage reads in its last two double columns.
+inline bool cb_on(const gk_ctx *c) { return c->basis == GK_BASIS_F32; }
+inline float *cb_base(const gk_ctx *c) { return reinterpret_cast<float *>(c->V); }
+inline float *cb_col(const gk_ctx *c, int k) { return cb_base(c) + (i64)k * c->ld; }
+inline double *cb_v1w(const gk_ctx *c) { return c->V + (i64)(c->m - 1) * c->ld; }
+inline double *cb_vjw(const gk_ctx *c) { return c->V + (i64)c->m * c->ld; }
 
 // gk_comm.hip
 bool collective(const gk_ctx *c);

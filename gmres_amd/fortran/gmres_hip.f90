@@ -25,6 +25,7 @@ module gmres_hip_c
     integer(c_int), parameter :: GK_OK = 0
     integer(c_int), parameter :: GK_PREC_IDENTITY = 0, GK_PREC_CBPR2 = 1, GK_PREC_CHEB = 2
     integer(c_int), parameter :: GK_SIDE_LEFT = 0, GK_SIDE_RIGHT = 1
+    integer(c_int), parameter :: GK_BASIS_F64 = 0, GK_BASIS_F32 = 1
     integer(c_int), parameter :: GK_VEC_X = 0, GK_VEC_B = 1
     integer(c_int), parameter :: GK_SR_PCG = 0, GK_SR_BICGSTAB = 1
     integer(c_int), parameter :: GK_LC_COPY = 0, GK_LC_AXPY = 1, GK_LC_AXPY2 = 2, GK_LC_XPAYMZ = 3, GK_LC_ZERO = 4
@@ -57,6 +58,16 @@ module gmres_hip_c
             import :: c_int, c_ptr
             type(c_ptr), value :: ctx
             integer(c_int), value :: side
+        end function
+        integer(c_int) function gk_set_basis_precision(ctx, prec) bind(C, name='gk_set_basis_precision')
+            import :: c_ptr, c_int
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: prec
+        end function
+        integer(c_int) function gk_get_basis_precision(ctx, prec) bind(C, name='gk_get_basis_precision')
+            import :: c_ptr, c_int
+            type(c_ptr), value :: ctx
+            integer(c_int), intent(out) :: prec
         end function
         integer(c_int) function gk_set_rhs(ctx, b) bind(C, name='gk_set_rhs')
             import :: c_int, c_ptr, c_double
@@ -297,7 +308,7 @@ module gmres_hip
     integer, parameter, public :: MGSR_OMP = 1, MGSR_MF = 0
 
     public :: stencil_vector, precond
-    public :: GK_SIDE_LEFT, GK_SIDE_RIGHT
+    public :: GK_SIDE_LEFT, GK_SIDE_RIGHT, GK_BASIS_F64, GK_BASIS_F32
     public :: hip_poisson5, hip_identity, hip_cbpr2, hip_chebyshev
     public :: gmres_mgsr_hip, gmres_hh_hip, gmres_hh_prec_hip, hip_release
     public :: pcg_hip, pbicgstab_hip, pcg_drive, bicgstab_drive, pcg_drive_seq, bicgstab_drive_seq
@@ -363,6 +374,12 @@ contains
     !> MGSR_MF: gmres_mgsr_mf (:98-199: exit inside the j loop).
     !> hist_res(c) = true residual after cycle c, hist_ferr(j,c) = final_err(j)
     !> of cycle c (written only when want_hist).  Returns a GK status.
+    !> On a compressed (FP32) basis (gk_get_basis_precision) one cycle resolves a residual
+    !> reduction of about 2^-24 only: beyond it final_err(j) keeps falling while the true
+    !> residual stops.  So a cycle whose final_err(j) falls below floor = 2^-20 g(1)/||b||
+    !> CLOSES at n_out = j (back-solve, update of x) without any convergence being
+    !> declared; the next cycle starts from the FP64 true residual and the existing exits
+    !> decide.  With an FP64 basis the driver is unchanged.
     integer function mgsr_drive(ctx, m, tol, beta0, variant, max_cyc, x, final_err, v_err, n_out, &
                                 restart_out, want_verr, want_hist, hist_res, hist_ferr, n_cycles, keep_x) &
         result(st)
@@ -375,19 +392,24 @@ contains
         real(8), intent(inout) :: hist_res(*), hist_ferr(m, *)
         logical, intent(in), optional :: keep_x  ! .true.: x stays in HBM (gk_get_x later)
         real(8), allocatable :: H(:, :), g(:), y(:), cs(:), sn(:), hcol(:)
-        real(8) :: beta, h_val
+        real(8) :: beta, h_val, floor_err
         integer :: cyc, j, zero_last
-        logical :: converged, exited
+        integer(c_int) :: bprec
+        logical :: converged, exited, cb, guarded
         allocate (H(m + 1, m), g(m + 1), y(m), cs(m), sn(m), hcol(m + 1))
         final_err = 0.0d0; v_err = 0.0d0; cs = 0.0d0; sn = 0.0d0
         n_out = 0; restart_out = 0; n_cycles = 0; h_val = 0.0d0
-        converged = .false.; exited = .false.
+        converged = .false.; exited = .false.; guarded = .false.
+        st = gk_get_basis_precision(ctx, bprec); if (st /= GK_OK) return
+        cb = bprec == GK_BASIS_F32
         st = gk_zero_x(ctx); if (st /= GK_OK) return     ! x0 = 0 (gmres_mgsr.f90:304)
         do cyc = 1, max_cyc
             g = 0.0d0; H = 0.0d0
             st = gk_mgs_cycle_start(ctx, beta); if (st /= GK_OK) return
             g(1) = beta
             exited = .false.
+            guarded = .false.
+            floor_err = 2.0d0**(-20)*(g(1)/beta0)
             ! Pipelined: step j+1 is enqueued on the GPU before the host waits for
             ! step j's Hessenberg column, so the Givens work below overlaps it.
             if (.not. converged) then
@@ -405,6 +427,13 @@ contains
                 call givens_column(H, cs, sn, g, j)
                 final_err(j) = abs(g(j + 1))/beta0
                 if (want_hist) hist_ferr(j, cyc) = final_err(j)
+                if (cb) then
+                    if (final_err(j) < floor_err) then   ! the basis's resolution: close the cycle, no verdict
+                        n_out = j
+                        guarded = .true.
+                        exit
+                    end if
+                end if
                 if (variant == MGSR_MF) then
                     if (h_val < tol .or. final_err(j) < tol) then
                         n_out = j
@@ -422,9 +451,11 @@ contains
             if (want_hist) then
                 st = gk_true_residual(ctx, hist_res(cyc)); if (st /= GK_OK) return
             end if
-            if (h_val < tol .or. final_err(n_out) < tol) then
-                restart_out = cyc
-                exit
+            if (.not. guarded) then
+                if (h_val < tol .or. final_err(n_out) < tol) then
+                    restart_out = cyc
+                    exit
+                end if
             end if
         end do
         if (restart_out == 0) restart_out = n_cycles
@@ -845,9 +876,11 @@ contains
     !> Optional variant = MGSR_MF reproduces gmres_mgsr_mf (:98-109).  Optional
     !> side = GK_SIDE_RIGHT preconditions on the right (w = A M^-1 v_j,
     !> x += M^-1 V y): final_err(j) is then the true relative residual, where the
-    !> reference's left side reports ||M^-1 (b - A x)|| / ||b||.
+    !> reference's left side reports ||M^-1 (b - A x)|| / ||b||.  Optional
+    !> basis = GK_BASIS_F32 stores the Krylov columns as FP32 (gk_set_basis_precision:
+    !> everything else stays FP64, the solve still converges to FP64 accuracy).
     subroutine gmres_mgsr_hip(Ax_vec, b, x, m, tol, final_err, v_err, n_out, restart_out, M_inv, params, variant, &
-                              side)
+                              side, basis)
         procedure(stencil_vector) :: Ax_vec
         real(8), intent(in) :: b(:)
         real(8), allocatable, intent(out) :: x(:)
@@ -857,7 +890,7 @@ contains
         integer, intent(out) :: n_out, restart_out
         procedure(precond) :: M_inv
         real(8), intent(in) :: params(:)
-        integer, intent(in), optional :: variant, side
+        integer, intent(in), optional :: variant, side, basis
         type(c_ptr) :: ctx
         integer(c_int) :: kind, degree, sd
         integer :: var, ncyc
@@ -870,6 +903,7 @@ contains
         if (present(side)) sd = int(side, c_int)
         allocate (x(size(b)), final_err(m), v_err(m + 1))
         ctx = solver_ctx(b, m, kind, degree, params, sd)
+        if (present(basis)) call gk_require(gk_set_basis_precision(ctx, int(basis, c_int)), 'gk_set_basis_precision')
         call gk_require(mgsr_drive(ctx, m, tol, norm2(b), var, hip_max_restarts, x, final_err, v_err, n_out, &
                                    restart_out, .true., .false., dummy_h, dummy_f, ncyc), 'gmres_mgsr_hip')
         call gk_require(gk_destroy(ctx), 'gk_destroy')

@@ -5,29 +5,32 @@
 !!   stvec -> hip_poisson5, cbpr2 -> hip_cbpr2,
 !!   gmres_hh_prec_omp -> gmres_hh_prec_hip, gmres_mgsr_omp -> gmres_mgsr_hip.
 !! An optional third argument `right` runs the MGS-R solve alone, preconditioned
-!! on the right (side = GK_SIDE_RIGHT: its "Final residual" is the true one).
+!! on the right (side = GK_SIDE_RIGHT: its "Final residual" is the true one); `f32`
+!! runs it alone on the compressed basis (basis = GK_BASIS_F32: the Krylov columns
+!! stored as FP32).
 program test_mfp_hip
     use gmres_hip
     implicit none
     integer :: nsize, max_iter, n_args
     character(len=32) :: arg_str
-    logical :: right
+    logical :: right, f32
     n_args = command_argument_count()
     if (n_args < 2) then
-        print *, "usage ./test_mfp_hip <grid size> <iterations per restart> [right]"
+        print *, "usage ./test_mfp_hip <grid size> <iterations per restart> [right|f32]"
         stop
     end if
-    right = .false.
+    right = .false.; f32 = .false.
     if (n_args >= 3) then
         call get_command_argument(3, arg_str)
         right = trim(arg_str) == 'right'
+        f32 = trim(arg_str) == 'f32'
     end if
     call get_command_argument(1, arg_str)
     read (arg_str, *) nsize
     call get_command_argument(2, arg_str)
     read (arg_str, *) max_iter
     write (*, '(60("-"))')
-    if (.not. right) then
+    if (.not. right .and. .not. f32) then
         call run(nsize, max_iter, .true.)
         write (*, '(60("-"))')
     end if
@@ -50,6 +53,8 @@ contains
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (Householder Chebyshev, MI355X)'
         else if (right) then
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR Chebyshev on the right, MI355X)'
+        else if (f32) then
+            write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR Chebyshev, compressed basis, MI355X)'
         else
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR Chebyshev, MI355X)'
         end if
@@ -60,6 +65,9 @@ contains
         else if (right) then
             call gmres_mgsr_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params, &
                                 side=GK_SIDE_RIGHT)
+        else if (f32) then
+            call gmres_mgsr_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params, &
+                                basis=GK_BASIS_F32)
         else
             call gmres_mgsr_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params)
         end if

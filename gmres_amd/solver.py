@@ -20,6 +20,7 @@ from . import _native as nat
 PREC = {"identity": nat.GK_PREC_IDENTITY, "none": nat.GK_PREC_IDENTITY,
         "cbpr2": nat.GK_PREC_CBPR2, "cheb": nat.GK_PREC_CHEB, "chebyshev": nat.GK_PREC_CHEB}
 SIDE = {"left": nat.GK_SIDE_LEFT, "right": nat.GK_SIDE_RIGHT}
+BASIS = {"f64": nat.GK_BASIS_F64, "f32": nat.GK_BASIS_F32}
 MGSR_MF, MGSR_OMP = 0, 1
 
 
@@ -199,6 +200,20 @@ class Context:
             nat.check(nat.hip().gk_set_precond_side(self._h, SIDE[side]), "gk_set_precond_side")
             self.side = side
 
+    def set_basis(self, basis: str = "f64") -> None:
+        """Storage precision of the MGS-R Krylov columns (gk_set_basis_precision): "f64"
+        (default) or "f32", the compressed basis -- columns stored as FP32, all arithmetic
+        FP64; single rank, m >= 3.  Ends an open cycle."""
+        if basis not in BASIS:
+            raise ValueError(f"basis must be 'f64' or 'f32', not {basis!r}")
+        nat.check(nat.hip().gk_set_basis_precision(self._h, BASIS[basis]), "gk_set_basis_precision")
+
+    @property
+    def basis(self) -> str:
+        v = ctypes.c_int()
+        nat.check(nat.hip().gk_get_basis_precision(self._h, ctypes.byref(v)), "gk_get_basis_precision")
+        return {b: a for a, b in BASIS.items()}[v.value]
+
     def set_rhs(self, b_local: np.ndarray) -> None:
         b = np.ascontiguousarray(b_local, dtype=np.float64).reshape(-1)
         assert b.size == self.nloc
@@ -361,6 +376,18 @@ def res_plan_query(nloc: int, cus: int = 256, share: int = 1, hh: bool = False, 
     return _res_dict(lambda buf: nat.hip().gk_res_plan_query(int(nloc), int(cus), int(share), int(hh), int(nt),
                                                              int(block), buf),
                      "gk_res_plan_query")
+
+
+def cb_plan_query(nloc: int, cus: int = 256, share: int = 1, m: int = 95) -> dict:
+    """The plan of the compressed-basis resident step (k_mgs_wcb) for a slab of nloc local
+    unknowns on a device of `cus` compute units shared by `share` contexts, Krylov
+    dimension m (gk_cb_plan_query: host-only, no GPU touched).  Chunks are 256 double2 of
+    w; nres2 + nstream2 = nloc // 2; "on": the resident launch applies."""
+    buf = (nat.c_ll * len(nat.CB_INFO_KEYS))()
+    nat.check(nat.hip().gk_cb_plan_query(int(nloc), int(cus), int(share), int(m), buf), "gk_cb_plan_query")
+    d = dict(zip(nat.CB_INFO_KEYS, (int(v) for v in buf)))
+    d["on"] = bool(d["on"])
+    return d
 
 
 def _alloc_hist(m: int, max_cycles: int, want_hist: bool):

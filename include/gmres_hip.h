@@ -180,6 +180,51 @@ int gk_set_precond(gk_ctx *ctx, int kind, const double *params, int nparams, int
 #define GK_SIDE_LEFT 0
 #define GK_SIDE_RIGHT 1
 int gk_set_precond_side(gk_ctx *ctx, int side);
+/* Storage precision of the Krylov basis in the MGS-R cycle (context state; default
+ * GK_BASIS_F64; beyond the reference).
+ *   GK_BASIS_F64  every column an FP64 vector (the reference).
+ *   GK_BASIS_F32  the compressed basis (CB-GMRES): a column is STORED as FP32 -- the new
+ *                 column is float(w_i / h), the division in FP64, one round-to-nearest-
+ *                 even conversion, 0 when h = 0 -- and widened exactly wherever it is
+ *                 read.  w, every dot, every AXPY, the Hessenberg column, the Givens
+ *                 rotations and x stay FP64, in the expressions and order of the FP64
+ *                 step, so the Arnoldi relation holds for the stored vectors and a
+ *                 restart, which recomputes the true residual in FP64, converges to
+ *                 FP64 accuracy.  A projection of the resident step (k_mgs_wcb) moves 8 B
+ *                 per unknown instead of 16.  Within one cycle the basis resolves a
+ *                 residual reduction of about 2^-24 only: the host drivers close a cycle
+ *                 once final_err(j) < 2^-20 g(1) / ||b|| without declaring convergence
+ *                 (the next cycle starts from the FP64 true residual).
+ *                 No allocation: FP32 column k lives at float offset k * ld of the basis
+ *                 allocation (its lower half); the operator stage reads two FP64 vectors
+ *                 from the free upper half, column 1 and the newest column widened, so no
+ *                 operator or preconditioner kernel changes (both sides apply).  Needs
+ *                 m >= 3 (GK_ERR_ARG) and a single-rank context: GK_ERR_STATE on a context
+ *                 with a communicator, and gk_comm_init* on an F32 context returns
+ *                 GK_ERR_STATE.  MGS-R only: gk_hh_cycle_start / gk_hh_step_async return
+ *                 GK_ERR_STATE.  GK_TUNE_RES_BLOCK > 1 and GK_TUNE_RES_PF are ignored
+ *                 (the strict projection order runs); the step runs as one resident
+ *                 launch (gk_res_info: GK_RES_CB) or, with GK_TUNE_RES 0, m + 1 > 500, or
+ *                 several contexts sharing the device without GK_TUNE_RES 1, launch by
+ *                 launch (hipGraph replays as with FP64 columns).  gk_update_x,
+ *                 gk_get_basis (the exact stored values, widened) and gk_mgs_verr (the
+ *                 tree-reduced Gram) read the float columns.  gk_sr_* and gk_vec_* are
+ *                 unaffected: they own their columns as FP64 and start from their own data.
+ * Setting the precision ends a running gk_sr_* solve and an open GMRES cycle (steps
+ * return GK_ERR_STATE until the next gk_mgs_cycle_start) and drops the captured step
+ * graphs.  Setting GK_BASIS_F64 again gives back the default solve bit for bit.
+ * gk_cb_plan_query: pure host computation of the resident F32 step's plan for a slab of
+ * nloc unknowns on cus / share compute units with Krylov dimension m;
+ * info[GK_CB_INFO_LEN]: workgroups G, RW, LW (register / LDS chunks of 256 double2 of w
+ * per thread the kernel is built for), r2e, l2e (those a workgroup uses), dynamic LDS
+ * bytes, resident double2, streamed double2, whether the resident launch applies, and
+ * the kernel's static LDS bytes. */
+#define GK_BASIS_F64 0
+#define GK_BASIS_F32 1
+#define GK_CB_INFO_LEN 10
+int gk_set_basis_precision(gk_ctx *ctx, int prec);
+int gk_get_basis_precision(gk_ctx *ctx, int *prec);
+int gk_cb_plan_query(long long nloc, int cus, int share, int m, long long *info);
 /* Right-hand side b (local part, host) or b = A*1 built on device
  * (the manufactured RHS of every reference driver, test_poisson_mf.f90:39-40). */
 int gk_set_rhs(gk_ctx *ctx, const double *b_local);
@@ -355,7 +400,11 @@ int gk_sync(gk_ctx *ctx);
  *   GK_RES_BLOCKED    k_mgs_blk (gmres_amd/csrc/gk_blk.hpp): the blocked-projection MGS-R
  *                     step of GK_TUNE_RES_BLOCK > 1 -- one all-gather per block of S
  *                     projections; r2 / l2 = cached column chunks per block slot in
- *                     registers / LDS, blk = S.
+ *                     registers / LDS, blk = S;
+ *   GK_RES_CB         k_mgs_wcb (gmres_amd/csrc/gk_cb.hpp): the step of a GK_BASIS_F32
+ *                     context on float columns -- w only, in registers + LDS, chunks of
+ *                     256 double2; r2 / l2 = the chunks the kernel is built for
+ *                     (gk_res_info only: gk_cb_plan_query is its planner).
  * info[GK_RES_INFO_LEN]: variant, workgroups G, R2, L2, prefetch, control
  * wave, w-only, non-temporal column loads, register / LDS chunks per
  * workgroup in use, dynamic LDS bytes, resident double2 of the slab, and
@@ -379,6 +428,7 @@ int gk_sync(gk_ctx *ctx);
 #define GK_RES_WONLY 4
 #define GK_RES_WCOL 5
 #define GK_RES_BLOCKED 6
+#define GK_RES_CB 7
 #define GK_RES_INFO_LEN 17
 int gk_res_plan_query(long long nloc, int cus, int share, int hh, int nt, int block, long long *info);
 int gk_res_info(gk_ctx *ctx, int hh, long long *info);
