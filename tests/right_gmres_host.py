@@ -83,10 +83,17 @@ def _back_solve(H, g, n_out, m):
 
 
 def gmres_mgsr_host(orc, N, m, prec="cbpr2", degree=8, side="left", tol=TOL, params=PARAMS,
-                    max_cycles=1000, b=None) -> HostResult:
+                    max_cycles=1000, b=None, threads=1) -> HostResult:
     assert side in ("left", "right")
     kind = {"identity": orc.PREC_IDENTITY, "cbpr2": orc.PREC_CBPR2, "cheb": orc.PREC_CHEB}[prec]
-    orc.set_threads(1)
+    orc.set_threads(threads)
+    try:
+        return _mgsr_host(orc, N, m, kind, degree, side, tol, params, max_cycles, b)
+    finally:
+        orc.set_threads(1)
+
+
+def _mgsr_host(orc, N, m, kind, degree, side, tol, params, max_cycles, b) -> HostResult:
     n = N * N
     b = orc.rhs_ones(N) if b is None else np.ascontiguousarray(b, dtype=np.float64)
     minv = lambda r: orc.precond(kind, r, N, params=params, degree=degree)  # noqa: E731

@@ -50,13 +50,13 @@ CASES = [
     (64, 20, "identity", 0, 1),      # fully resident, R2 = 2, prefetch
     (130, 30, "cbpr2", 2, 8),        # 32 workgroups x 512 x 2 < n/2: streamed tail of the vector
     (45, 12, "identity", 2, 64),     # odd N: the tail element, 4 workgroups
-    (256, 40, "cheb", 12, 16),       # two-array variant (+ LDS-resident w)
+    (256, 40, "cheb", 12, 16),       # 16 workgroups x 5 chunks: R2 = 8 (prefetch), partly used
     (200, 25, "identity", 4, 32),    # R2 = 4 with a streamed part
     (512, 30, "identity", 8, 4),     # R2 = 8, fully resident
     # even spread of the resident chunks (ResPlan::r2e / l2e): register part and
     # LDS part only partly used, as at 2048^2 with every CU
     (1024, 10, "identity", 0, 2),    # auto variant, 128 workgroups
-    (700, 12, "cbpr2", 12, 4),       # two-array variant, LDS part partly filled
+    (700, 12, "cbpr2", 12, 4),       # two-array variant (pairs), 8 of 12 register chunks used
     (2048, 8, "identity", 0, 1),     # the size whose contiguous fill idled 70 % of the workgroups
 ]
 
@@ -134,7 +134,7 @@ HCASES = [
     (64, 20, "identity", 0, 1, -1),     # fully resident, R2 = 2, prefetch
     (45, 12, "cbpr2", 2, 64, -1),       # odd N (tail element), streamed part
     (200, 25, "identity", 4, 32, -1),   # R2 = 4 with a streamed part
-    (256, 40, "identity", 12, 16, -1),  # two-array variant + LDS-resident w
+    (256, 40, "identity", 12, 16, -1),  # R2 = 8 (prefetch), 5 chunks per workgroup
     (300, 20, "identity", 12, 64, 1),   # w-only: registers + LDS + streamed
     (181, 16, "cbpr2", 12, 128, 1),     # w-only, odd N
 ]
