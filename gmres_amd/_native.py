@@ -116,6 +116,7 @@ _SIGS = {
     "gk_zero_x": (c_int, [c_vp]),
     "gk_get_x": (c_int, [c_vp, _dp]),
     "gk_get_basis": (c_int, [c_vp, c_int, c_int, _dp]),
+    "gk_set_basis": (c_int, [c_vp, c_int, _dp]),
     "gk_set_x": (c_int, [c_vp, _dp]),
     "gk_apply": (c_int, [c_vp, c_int, _dp, _dp]),
     "gk_true_residual": (c_int, [c_vp, _dp]),

@@ -14,6 +14,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1225,6 +1226,39 @@ int gk_get_basis(gk_ctx *c, int which, int col, double *out) {
         src = c->aux;
     }
     HIPCHK(hipMemcpyAsync(out, src, sizeof(double) * c->nloc, hipMemcpyDeviceToHost, c->st));
+    CHK(sync_st(c));
+    return GK_OK;
+}
+
+// The inverse of gk_get_basis(which = 0).  FP32 basis: the values must be floats already
+// (a second rounding here would hide the one under test); the column, and its widened
+// copy in vjw (and in v1w when col == 0), exactly as k_scale_cb leaves them.
+int gk_set_basis(gk_ctx *c, int col, const double *in) {
+    CHK(check_ctx(c));
+    if (in == nullptr) return set_err(GK_ERR_ARG, "null column");
+    if (col < 0 || col > c->m) return set_err(GK_ERR_ARG, "bad column %d", col);
+    std::vector<float> f;
+    if (cb_on(c)) {
+        f.resize((size_t)c->nloc);
+        for (i64 e = 0; e < c->nloc; ++e) {
+            // finite and within float's range first: converting a larger double is undefined
+            const bool in_range = std::fabs(in[e]) <= (double)FLT_MAX;
+            f[(size_t)e] = in_range ? (float)in[e] : 0.0f;
+            if (!in_range || (double)f[(size_t)e] != in[e])
+                return set_err(GK_ERR_ARG, "gk_set_basis: element %lld of column %d is not an FP32 value (FP32 basis)",
+                               (long long)e, col);
+        }
+    }
+    sr_invalidate(c);  // the short-recurrence vectors share the allocation
+    HIPCHK(hipSetDevice(c->dev));
+    const size_t nb = sizeof(double) * (size_t)c->nloc;
+    if (cb_on(c)) {
+        HIPCHK(hipMemcpyAsync(cb_col(c, col), f.data(), sizeof(float) * (size_t)c->nloc, hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemcpyAsync(cb_vjw(c), in, nb, hipMemcpyHostToDevice, c->st));
+        if (col == 0) HIPCHK(hipMemcpyAsync(cb_v1w(c), in, nb, hipMemcpyHostToDevice, c->st));
+    } else {
+        HIPCHK(hipMemcpyAsync(c->V + (i64)col * c->ld, in, nb, hipMemcpyHostToDevice, c->st));
+    }
     CHK(sync_st(c));
     return GK_OK;
 }

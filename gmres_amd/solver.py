@@ -240,6 +240,15 @@ class Context:
         nat.check(nat.hip().gk_get_basis(self._h, which, col, _p(v)), "gk_get_basis")
         return v
 
+    def put_basis(self, col: int, v: np.ndarray) -> None:
+        """The inverse of get_basis(col) (gk_set_basis; test support): v into column col
+        (0-based, 0..m) of V.  On the "f32" basis v must hold float32 values exactly
+        (GkError otherwise, nothing written) and also becomes the next step's operator
+        input: plant column j - 1 last before mgs_step(j)."""
+        vv = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        assert vv.size == self.nloc
+        nat.check(nat.hip().gk_set_basis(self._h, int(col), _p(vv)), "gk_set_basis")
+
     def set_x(self, x: np.ndarray) -> None:
         xx = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
         nat.check(nat.hip().gk_set_x(self._h, _p(xx)), "gk_set_x")

@@ -241,6 +241,20 @@ int gk_get_x(gk_ctx *ctx, double *x_local);
  * Diagnostic only (the orthogonality tests evaluate the reference's formula on
  * the device basis). */
 int gk_get_basis(gk_ctx *ctx, int which, int col, double *out);
+/* The inverse of gk_get_basis(which = 0): overwrite column col (0-based, 0..m) of the
+ * MGS-R Krylov basis / the Householder reflectors with in[0..nloc).  Diagnostic / test
+ * support only (the single-step tests plant known columns in an open cycle).
+ * FP64 basis: the nloc doubles are copied as they are.
+ * FP32 basis: every value must be finite and exactly representable as a float, otherwise
+ * GK_ERR_ARG and nothing is written (no silent second rounding).  The values are stored
+ * as floats; the same values widened become the operator's input (vjw), and the first
+ * dot's partner (v1w) when col = 0 -- the state a cycle leaves that produced this column
+ * last.  The column set LAST is therefore the next step's operator input: plant column
+ * j - 1 last before gk_mgs_step(j).
+ * Ends a running gk_sr_* solve (its vectors share the allocation), as gk_set_x does; does
+ * not close an open GMRES cycle and does not touch the captured step graphs (they hold
+ * pointers only). */
+int gk_set_basis(gk_ctx *ctx, int col, const double *in);
 int gk_set_x(gk_ctx *ctx, const double *x_local);
 /* Host-array operator application on this context's slab (clobbers the
  * work vectors; not between cycle start and update):  what = 0: out = A in

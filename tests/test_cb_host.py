@@ -48,7 +48,7 @@ def test_cb_plan_large_m_is_the_launch_path():
 def test_cabi_names_of_the_compressed_basis():
     from gmres_amd import _native as nat
 
-    for name in ("gk_set_basis_precision", "gk_get_basis_precision", "gk_cb_plan_query"):
+    for name in ("gk_set_basis_precision", "gk_get_basis_precision", "gk_cb_plan_query", "gk_set_basis"):
         assert name in nat._SIGS and name in nat.header_symbols()
     hdr = open(os.path.join(ROOT, "include", "gmres_hip.h")).read()
     for line in ("#define GK_BASIS_F64 0", "#define GK_BASIS_F32 1", "#define GK_RES_CB 7",

@@ -31,6 +31,10 @@ planted data) from mgs_step_ld, never below the strict bound; on the CPU that de
 (tests/test_general_data.py::test_blocked_step_emulation).  Because that is wide, the blocked
 step is also held to the STRICT bound against the long-double evaluation of its own order.
 
+test_preconditioned_step runs the step behind cbpr2 and Chebyshev(k) on either side, where the
+first dot <w, V(:,1)> comes from the operator launch's epilogue instead of the stencil's; the
+FP32-basis step has the same cases in test_gpu_cb_step_known_answer.py.
+
 The same planted contexts check gk_update_x, gk_mgs_verr, gk_vec_dot and the gk_vec_lincomb
 forms against long-double / exact float64 evaluations.
 """
@@ -42,8 +46,8 @@ import pytest
 
 from tests import test_gpu_blocked as tb
 from tests import test_gpu_resident as tr
-from tests.general_data import (EPS, MARGIN, blocked_step, check_step, mgs_step_ld, plant, planted_basis, read_col,
-                                step_bounds)
+from tests.general_data import (PREC_STEP_CASES, EPS, MARGIN, PARAMS, blocked_step, check_step, mgs_step_ld, op_w0, plant,
+                                planted_basis, read_col, step_bounds)
 
 pytestmark = pytest.mark.gpu
 
@@ -61,12 +65,13 @@ def _V(N, m):
     return _basis[(N, m)]
 
 
-def _ref(oracle, N, m, j):
-    """(V[:j], w0, (h_ref, v_ref)) of step j on the planted columns; once per case."""
-    key = (N, m, j)
+def _ref(oracle, N, m, j, op=None):
+    """(V[:j], w0, (h_ref, v_ref)) of step j on the planted columns; once per case.
+    op = (side, kind, degree): the preconditioned operator instead of A."""
+    key = (N, m, j) if op is None else (N, m, j, op)
     if key not in _refs:
         V = _V(N, m)[:j]
-        w0 = oracle.stvec(V[j - 1], N)
+        w0 = oracle.stvec(V[j - 1], N) if op is None else op_w0(oracle, V[j - 1], N, *op)
         _refs[key] = (V, w0, mgs_step_ld(V, w0))
     return _refs[key]
 
@@ -79,16 +84,16 @@ def _blk_ref(N, m, j, S, V, w0):
     return _refs[key]
 
 
-def _open(N, m, tunes, side="left", **kw):
+def _open(N, m, tunes, side="left", prec=("identity", 1), **kw):
     """A context with its tuning applied and an MGS-R cycle open on the identity
-    preconditioner; every column 0..m-1 planted."""
+    preconditioner (or prec = (kind, degree)); every column 0..m-1 planted."""
     import gmres_amd as ga
 
     c = ga.Context(N, m, **kw)
     try:
         for k, v in tunes:
             c.tune(k, v)
-        c.set_precond("identity", side=side)
+        c.set_precond(prec[0], PARAMS, prec[1], side=side)
         c.set_rhs_ones()
         c.mgs_cycle_start()
         V = _V(N, m)
@@ -110,11 +115,11 @@ def _step(c, N, m, j):
     return h, v
 
 
-def _check(oracle, c, N, m, js, what, twice=False):
+def _check(oracle, c, N, m, js, what, twice=False, op=None):
     worst = (0.0, 0.0)
     plan = c.res_info()
     for j in js:
-        V, w0, ref = _ref(oracle, N, m, j)
+        V, w0, ref = _ref(oracle, N, m, j, op)
         for rep in range(2 if twice else 1):
             h, v = _step(c, N, m, j)
             r = check_step(h, v, V, w0, ref, f"{what} N={N} m={m} j={j}" + (" (replay)" if rep else ""), plan=plan)
@@ -262,6 +267,46 @@ def test_right_identity_step_is_the_left_step(oracle):
         assert np.array_equal(hl, hr) and np.array_equal(vl, vr)
         V, w0, ref = _ref(oracle, N, m, j)
         check_step(hr, vr, V, w0, ref, f"right identity N={N} j={j}")
+
+
+# ----------------------------- the first dot from the operator launch's epilogue ---
+
+@pytest.mark.parametrize("route", ["launch", "resident"])
+@pytest.mark.parametrize("case", PREC_STEP_CASES, ids=[c[0] for c in PREC_STEP_CASES])
+def test_preconditioned_step(oracle, case, route):
+    """Every case above runs on the identity, whose first dot <w, V(:,1)> is the stencil's.
+    With a preconditioner it comes from the operator launch's epilogue: cbpr2, the Chebyshev
+    pass's ACC_DOT over overlapping windows (one fused pass, two passes, per-sweep kernels;
+    the stencil as stage 0 of the pass and as a launch of its own), k_right_cbpr2 and its
+    two-launch form, Chebyshev(3) on the right.  w0 is the oracle's M^-1 A v (right: A M^-1 v),
+    bit-exact with the device operators; the bounds are the identity cases'.  j = 1, 2, m on
+    the launch path, and on the resident step forced to w-only on two workgroups (where a
+    workgroup's share is under eight chunks, 45^2 and 65^2, the prefetch variant runs)."""
+    from gmres_amd import _native as nat
+    from tests.test_gpu_wres_carry import _workgroups_share
+
+    _, side, kind, degree, named, N, m = case
+    tunes = [(getattr(nat, k), v) for k, v in named]
+    if route == "launch":
+        tunes += [(T_RES, 0)]
+    else:
+        tunes += _res_tunes(12, _workgroups_share(2), 1, 0)
+    c = _open(N, m, tunes, side=side, prec=(kind, degree))
+    with c:
+        plan = c.res_info()
+        print(f"{case[0]} {route}: {plan}")
+        if route == "launch":
+            assert plan["variant"] is None, plan
+        else:
+            assert plan["variant"] == ("w-only" if N >= 130 else "prefetch") and plan["G"] == 2, plan
+        c.profile(True)
+        c.profile_reset()
+        _check(oracle, c, N, m, [1, 2, m], f"{case[0]} {route}", op=(side, kind, degree))
+        prof = c.profile_read()
+    if route == "launch":
+        assert prof["res"][1] == 0, prof
+    else:
+        assert prof["res"][1] == 3 and prof["proj"][1] == 0, prof  # one resident launch per step
 
 
 # ------------------------------------------------- three ranks, uneven slabs ----
