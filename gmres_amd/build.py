@@ -40,7 +40,9 @@ GK_CF_PARTS = 4
 HIP_UNITS = ([(HIP_SOURCES[0], [], "gk_api.o")] + [(HIP_SOURCES[1], [f"GK_CF_PART={p}"], f"gk_cheb{p}.o")
                                                     for p in range(GK_CF_PARTS)]
              + [(s, [], os.path.basename(s)[:-4] + ".o") for s in HIP_SOURCES[2:6]])
-# ... and the unit of the opt-in FP32-compressed basis (HIP_UNITS stays the FP64 solvers' list)
+# ... and the unit of the opt-in FP32-compressed basis: its resident step, scale and widening copy (its
+# launch-path projection, x update and Gram are float instantiations in gk_api's unit); HIP_UNITS stays
+# the FP64 solvers' list
 HIP_UNITS_CB = [(HIP_SOURCES[6], [], "gk_cb.o")]
 HIP_HEADERS = [os.path.join(CSRC, h) for h in ("gk_common.hpp", "gk_kernels.hpp", "gk_cheb.hpp", "gk_res.hpp",
                                                 "gk_blk.hpp", "gk_sr.hpp", "gk_host.hpp", "gk_resident.hpp",

@@ -214,34 +214,35 @@ int right_cbpr2(gk_ctx *c, const double *v, double *out, int acc, const double *
     return c->vec == 2 ? launch_right_v<2>(c, acc, a) : launch_right_v<1>(c, acc, a);
 }
 
-template <bool NT, int U>
-void launch_proj_u(gk_ctx *c, int mode, double *w, const double *va, const double *vb, const double *pin,
-                   int npin, double *pout, double *hslot, double coef, i64 tail0, int hstore) {
+// T: the type va / vb are stored in (float: the FP32 basis, PJ_AXPY_DOT / PJ_AXPY_NORM only)
+template <bool NT, int U, class T>
+void launch_proj_u(gk_ctx *c, int mode, double *w, const T *va, const T *vb, const double *pin, int npin,
+                   double *pout, double *hslot, double coef, i64 tail0, int hstore) {
     const dim3 g(c->np_pj);
     const i64 n = c->nloc;
-    switch (mode) {
-        case gk::PJ_DOT:
+    if constexpr (std::is_same<T, double>::value) {
+        if (mode == gk::PJ_DOT) {
             gk::k_proj<gk::PJ_DOT, NT, U><<<g, gk::TPB, 0, c->st>>>(w, va, vb, pin, npin, pout, hslot, coef, n,
                                                                     tail0, 0, hstore);
-            break;
-        case gk::PJ_AXPY:
+            return;
+        }
+        if (mode == gk::PJ_AXPY) {
             gk::k_proj<gk::PJ_AXPY, NT, U><<<g, gk::TPB, 0, c->st>>>(w, va, vb, pin, npin, pout, hslot, coef, n,
                                                                      tail0, 0, hstore);
-            break;
-        case gk::PJ_AXPY_DOT:
-            gk::k_proj<gk::PJ_AXPY_DOT, NT, U><<<g, gk::TPB, 0, c->st>>>(w, va, vb, pin, npin, pout, hslot, coef,
-                                                                         n, tail0, 0, hstore);
-            break;
-        default:
-            gk::k_proj<gk::PJ_AXPY_NORM, NT, U><<<g, gk::TPB, 0, c->st>>>(w, va, vb, pin, npin, pout, hslot, coef,
-                                                                          n, tail0, 0, hstore);
-            break;
+            return;
+        }
     }
+    if (mode == gk::PJ_AXPY_DOT)
+        gk::k_proj<gk::PJ_AXPY_DOT, NT, U, T><<<g, gk::TPB, 0, c->st>>>(w, va, vb, pin, npin, pout, hslot, coef, n,
+                                                                        tail0, 0, hstore);
+    else
+        gk::k_proj<gk::PJ_AXPY_NORM, NT, U, T><<<g, gk::TPB, 0, c->st>>>(w, va, vb, pin, npin, pout, hslot, coef, n,
+                                                                         tail0, 0, hstore);
 }
 
-template <bool NT>
-void launch_proj(gk_ctx *c, int mode, double *w, const double *va, const double *vb, const double *pin,
-                 int npin, double *pout, double *hslot, double coef, i64 tail0, int hstore) {
+template <bool NT, class T>
+void launch_proj(gk_ctx *c, int mode, double *w, const T *va, const T *vb, const double *pin, int npin,
+                 double *pout, double *hslot, double coef, i64 tail0, int hstore) {
     // loads in flight per thread and array: one trip per thread when the vector is small, else 2
     const i64 per_thread = (c->nloc / 2 + (i64)c->np_pj * gk::TPB - 1) / ((i64)c->np_pj * gk::TPB);
     if (per_thread > 4)
@@ -250,8 +251,12 @@ void launch_proj(gk_ctx *c, int mode, double *w, const double *va, const double 
         launch_proj_u<NT, 4>(c, mode, w, va, vb, pin, npin, pout, hslot, coef, tail0, hstore);
 }
 
-int proj(gk_ctx *c, int mode, double *w, const double *va, const double *vb, const double *pin,
-         int npin, double *pout, double *hslot, double coef, i64 tail0 = 0, int hstore = 0) {
+// (T is named, never deduced: callers pass nullptr for the column a mode does not read)
+template <class T = double>
+int proj(gk_ctx *c, int mode, double *w, const std::common_type_t<T> *va, const std::common_type_t<T> *vb,
+         const double *pin, int npin, double *pout, double *hslot, double coef, i64 tail0 = 0, int hstore = 0) {
+    if (!std::is_same<T, double>::value && mode != gk::PJ_AXPY_DOT && mode != gk::PJ_AXPY_NORM)
+        return set_err(GK_ERR_STATE, "projection mode %d on float columns", mode);
     ProfScope ps(c, GK_KID_PROJ);
     if (c->tune_nt > 0 || (c->tune_nt < 0 && c->nt_auto))
         launch_proj<true>(c, mode, w, va, vb, pin, npin, pout, hslot, coef, tail0, hstore);
@@ -266,6 +271,30 @@ int scale(gk_ctx *c, double *out, const double *w, const double *pin, int npin, 
     ProfScope ps(c, GK_KID_SCALE);
     gk::k_scale<<<c->nblk_stream, gk::TPB, 0, c->st>>>(out, w, pin, npin, hslot, c->nloc, hcopy, hsrc, ncopy,
                                                        pin_norm ? 1 : 0);
+    LAUNCHCHK();
+    return GK_OK;
+}
+
+// V(:,k+1) = w / h, h = sqrt(sum(pin)), in the basis' own type; the FP32 basis also widens the
+// new column to vjw (the operator's next input) and, for column 1, to v1w (the first dot's partner)
+int scale_col(gk_ctx *c, int k, const double *pin, int npin, double *hslot, double *hcopy = nullptr,
+              const double *hsrc = nullptr, int ncopy = 0) {
+    if (!cb_on(c)) return scale(c, vcol<double>(c, k), c->w, pin, npin, hslot, hcopy, hsrc, ncopy);
+    ProfScope ps(c, GK_KID_SCALE);
+    HIPCHK(gk::cb_scale(c->nblk_stream, vcol<float>(c, k), cb_vjw(c), k == 0 ? cb_v1w(c) : nullptr, c->w, pin, npin,
+                        hslot, c->nloc, hcopy, hsrc, ncopy, c->st));
+    return GK_OK;
+}
+
+// x (+)= V(:, 1:n_out) ydev on the basis as it is stored
+template <bool ADD, class T>
+void launch_update_x(gk_ctx *c, double *x, int n_out) {
+    gk::k_update_x<ADD, T><<<c->nblk_stream, gk::TPB, 0, c->st>>>(x, vcol<T>(c, 0), c->ld, c->ydev, n_out, c->nloc);
+}
+template <bool ADD>
+int update_x(gk_ctx *c, double *x, int n_out) {
+    ProfScope ps(c, GK_KID_UPDATE);
+    cb_on(c) ? launch_update_x<ADD, float>(c, x, n_out) : launch_update_x<ADD, double>(c, x, n_out);
     LAUNCHCHK();
     return GK_OK;
 }
@@ -321,43 +350,32 @@ bool res_plan(gk_ctx *c, ResPlan &p, bool hh = false) {
 //    writes w(1:j+1) to c->hb (one more exchange); RESF_UNIT_INIT -- RES_HH_DOWN builds
 //    its unit input e_{unit_g} itself.
 enum { RESF_CLOSE_HH = 1, RESF_UNIT_INIT = 2, RESF_PIN_LOCAL = 4 };
-int res_step(gk_ctx *c, int j, const ResPlan &p, const double *pin, int npin, double *hs, double *hcopy,
-             int mode = gk::RES_MGS, double *w = nullptr, i64 unit_g = -1, int flags = 0) {
-    ProfScope ps(c, GK_KID_RES);
-    const bool close = (flags & RESF_CLOSE_HH) && mode == gk::RES_HH_UP;
-    if ((flags & ~RESF_PIN_LOCAL) != 0 && !p.wo)
-        return set_err(GK_ERR_STATE, "resident flags %d need the w-only variant", flags);
-    const bool pin_local = (flags & RESF_PIN_LOCAL) && mode != gk::RES_HH_DOWN && c->xs_on && c->nranks > 1;
-    // exchanges of the launch
-    const int np = (mode == gk::RES_MGS ? (p.bvar >= 0 ? gk::blk_exchanges(j, p.blk) : 2 * j) : j) + (close ? 1 : 0);
+
+// What a resident launch of step j with np exchanges takes from the context, whichever
+// basis it runs on (Plan: ResPlan or gk::CbPlan): w, the first dot's slab, the H column's
+// two destinations, the plan's split of w, the all-gather's granule region, tags and
+// timeout, the error word, the stamps and the trace hook -- for one rank.
+template <class Plan>
+int res_args(gk_ctx *c, int j, int mode, const Plan &p, int np, const double *pin, int npin, double *hs,
+             double *hcopy, gk::ResArgs &a) {
     if (c->res_tag > 0xF0000000u) {  // tags must never repeat within the granule region's lifetime
         HIPCHK(hipMemsetAsync(c->res_gath, 0, sizeof(gk::u64) * gk::RES_GATH_ALL, c->st));
         c->res_tag = 1;
     }
-    gk::ResArgs a{};
-    a.w = w != nullptr ? w : c->w;
+    a.w = c->w;
     a.mode = mode;
     a.coef = mode == gk::RES_MGS ? 1.0 : 2.0;
-    a.tail0 = mode == gk::RES_HH_UP ? (i64)j - c->g0 : 0;
-    a.V = c->V;
-    a.vout = c->V + (i64)j * c->ld;
     a.ld = c->ld;
     a.pin = pin;
     a.npin = npin;
     a.hs = hs;
     a.hcopy = hcopy;
     a.gath = c->res_gath;
-    a.gm = c->res_gm;
     a.j = j;
     a.n = c->nloc;
     a.nres2 = p.nres2;
     a.r2e = p.r2e;
     a.l2e = p.l2e;
-    a.unit_known = mode == gk::RES_HH_DOWN && unit_g >= 0;
-    a.unit_e = (a.unit_known && unit_g >= c->g0 && unit_g < c->g0 + c->nloc) ? unit_g - c->g0 : -1;
-    a.unit_init = a.unit_known && (flags & RESF_UNIT_INIT) ? 1 : 0;
-    a.close_hh = close ? 1 : 0;
-    a.hb = c->hb;
     a.tag0 = c->res_tag;
     c->res_tag += (unsigned)np;
     a.timeout = (gk::u64)c->res_timeout_ms * (gk::u64)c->xs_tick_per_ms;
@@ -368,10 +386,34 @@ int res_step(gk_ctx *c, int j, const ResPlan &p, const double *pin, int npin, do
         c->res_trace_g = p.G;
         c->res_trace_np = np;
     }
+    a.nranks = 1;
+    return GK_OK;
+}
+
+int res_step(gk_ctx *c, int j, const ResPlan &p, const double *pin, int npin, double *hs, double *hcopy,
+             int mode = gk::RES_MGS, double *w = nullptr, i64 unit_g = -1, int flags = 0) {
+    ProfScope ps(c, GK_KID_RES);
+    const bool close = (flags & RESF_CLOSE_HH) && mode == gk::RES_HH_UP;
+    if ((flags & ~RESF_PIN_LOCAL) != 0 && !p.wo)
+        return set_err(GK_ERR_STATE, "resident flags %d need the w-only variant", flags);
+    const bool pin_local = (flags & RESF_PIN_LOCAL) && mode != gk::RES_HH_DOWN && c->xs_on && c->nranks > 1;
+    // exchanges of the launch
+    const int np = (mode == gk::RES_MGS ? (p.bvar >= 0 ? gk::blk_exchanges(j, p.blk) : 2 * j) : j) + (close ? 1 : 0);
+    gk::ResArgs a{};
+    CHK(res_args(c, j, mode, p, np, pin, npin, hs, hcopy, a));
+    if (w != nullptr) a.w = w;
+    a.tail0 = mode == gk::RES_HH_UP ? (i64)j - c->g0 : 0;
+    a.V = c->V;
+    a.vout = c->V + (i64)j * c->ld;
+    a.gm = c->res_gm;
+    a.unit_known = mode == gk::RES_HH_DOWN && unit_g >= 0;
+    a.unit_e = (a.unit_known && unit_g >= c->g0 && unit_g < c->g0 + c->nloc) ? unit_g - c->g0 : -1;
+    a.unit_init = a.unit_known && (flags & RESF_UNIT_INIT) ? 1 : 0;
+    a.close_hh = close ? 1 : 0;
+    a.hb = c->hb;
     // auto: on -- A/B at 2896^2 (k_mgs_res<12, 18> NT, profiles/r04/ab_qdef_2896_r04a.jsonl): 19.98 /
     // 19.90 -> 18.82 / 18.84 us per projection
     a.qdef = c->tune_res_qdef != 0 ? 1 : 0;
-    a.nranks = 1;
     if (c->xs_on && c->nranks > 1) {
         a.err = c->xs_err_dev;
         a.timeout = std::max(a.timeout, c->xs_timeout);
@@ -397,42 +439,13 @@ bool cb_plan_ctx(gk_ctx *c, gk::CbPlan &p) {
     return p.on;
 }
 
-// The resident launch of step j on float columns: res_step's RES_MGS arguments.
+// The resident launch of step j on float columns (2 j exchanges): res_step's RES_MGS arguments.
 int cb_step(gk_ctx *c, int j, const gk::CbPlan &p, const double *pin, int npin, double *hs, double *hcopy) {
     ProfScope ps(c, GK_KID_RES);
-    const int np = 2 * j;
-    if (c->res_tag > 0xF0000000u) {  // tags must never repeat within the granule region's lifetime
-        HIPCHK(hipMemsetAsync(c->res_gath, 0, sizeof(gk::u64) * gk::RES_GATH_ALL, c->st));
-        c->res_tag = 1;
-    }
     gk::ResArgs a{};
-    a.w = c->w;
-    a.mode = gk::RES_MGS;
-    a.coef = 1.0;
-    a.ld = c->ld;
-    a.pin = pin;
-    a.npin = npin;
-    a.hs = hs;
-    a.hcopy = hcopy;
-    a.gath = c->res_gath;
-    a.j = j;
-    a.n = c->nloc;
-    a.nres2 = p.nres2;
-    a.r2e = p.r2e;
-    a.l2e = p.l2e;
-    a.tag0 = c->res_tag;
-    c->res_tag += (unsigned)np;
-    a.timeout = (gk::u64)c->res_timeout_ms * (gk::u64)c->xs_tick_per_ms;
-    a.err = c->res_err_dev;
-    a.stamps = c->res_split ? c->res_stamps : nullptr;
-    if (c->res_trace != nullptr && j == c->res_trace_j && c->res_trace_mode == gk::RES_MGS) {
-        a.trace = c->res_trace;
-        c->res_trace_g = p.G;
-        c->res_trace_np = np;
-    }
-    a.nranks = 1;
+    CHK(res_args(c, j, gk::RES_MGS, p, 2 * j, pin, npin, hs, hcopy, a));
     std::string msg;
-    const int e = gk::cb_launch(p, a, cb_base(c), cb_vjw(c), c->dev, c->st, msg);
+    const int e = gk::cb_launch(p, a, vcol<float>(c, 0), cb_vjw(c), c->dev, c->st, msg);
     return e == GK_OK ? GK_OK : set_err(e, "%s", msg.c_str());
 }
 
@@ -762,6 +775,12 @@ int ensure_gram(gk_ctx *c, int ncols) {
     return GK_OK;
 }
 
+// k_gram of the first ncols columns of base, stored as T, into the context's slab
+template <class T>
+void gram_slab(gk_ctx *c, const T *base, int ncols, int np) {
+    gk::k_gram<T><<<c->gram_nblk, gk::TPB, 0, c->st>>>(base, c->ld, ncols, c->nloc, c->gram_pairs, np, c->gram_slab);
+}
+
 // G (host, c x c symmetric, column-major) of the first c columns of base.
 int gram(gk_ctx *c, const double *base, int ncols, std::vector<double> &G) {
     CHK(ensure_gram(c, ncols));
@@ -770,20 +789,14 @@ int gram(gk_ctx *c, const double *base, int ncols, std::vector<double> &G) {
         for (int aa = 0; aa <= bb; ++aa) pr.push_back(make_short2((short)aa, (short)bb));
     const int np = (int)pr.size();
     HIPCHK(hipMemcpyAsync(c->gram_pairs, pr.data(), sizeof(short2) * np, hipMemcpyHostToDevice, c->st));
-    if (cb_on(c) && base == c->V) {  // float columns: the tree (no reference to match in its order)
-        ProfScope ps(c, GK_KID_OTHER);
-        HIPCHK(gk::cb_gram(c->gram_nblk, cb_base(c), c->ld, ncols, c->nloc, c->gram_pairs, np, c->gram_slab, c->st));
-        gk::k_gram_reduce<<<(np + gk::TPB - 1) / gk::TPB, gk::TPB, 0, c->st>>>(c->gram_slab, c->gram_nblk,
-                                                                            np, c->gram_out);
-        LAUNCHCHK();
-    } else if (verr_ref_order(c)) {  // one running sum per pair, k in order (the reference's dot_product)
+    const bool f32 = cb_on(c) && base == c->V;  // float columns: the tree (no reference to match in its order)
+    if (!f32 && verr_ref_order(c)) {  // one running sum per pair, k in order (the reference's dot_product)
         ProfScope ps(c, GK_KID_OTHER);
         gk::k_seqdot_pairs<<<(np + 63) / 64, 64, 0, c->st>>>(base, c->ld, c->nloc, c->gram_pairs, np, c->gram_out);
         LAUNCHCHK();
     } else {
         ProfScope ps(c, GK_KID_OTHER);
-        gk::k_gram<<<c->gram_nblk, gk::TPB, 0, c->st>>>(base, c->ld, ncols, c->nloc, c->gram_pairs, np,
-                                                        c->gram_slab);
+        f32 ? gram_slab(c, vcol<float>(c, 0), ncols, np) : gram_slab(c, base, ncols, np);
         LAUNCHCHK();
         gk::k_gram_reduce<<<(np + gk::TPB - 1) / gk::TPB, gk::TPB, 0, c->st>>>(c->gram_slab, c->gram_nblk,
                                                                             np, c->gram_out);
@@ -836,11 +849,9 @@ int reflect_chain_down(gk_ctx *c, double *v, int k, i64 unit_g = -1, int flags =
 // (AXPY_i fused with dot_{i+1}), each dot all-reduced, then h = ||w|| and
 // V(:,j+1) = w / h with H(1:j+1, j) published to mapped host memory.
 // gmres_mgsr.f90:341-363, :384.
-int mgs_chain_cb(gk_ctx *c, int j, int np);
-int mgs_chain(gk_ctx *c, int j, int np) {
-    if (cb_on(c)) return mgs_chain_cb(c, j, np);
-    const i64 ld = c->ld;
-    double *V = c->V;
+// T: the type the basis is stored in; the FP32 basis' closing also writes vjw (scale_col).
+template <class T>
+int mgs_chain_t(gk_ctx *c, int j, int np) {
     const int m2 = c->m + 2;
     double *hs = c->hall + (i64)(j - 1) * m2;
     int s0 = 0, s1 = 1;
@@ -848,48 +859,24 @@ int mgs_chain(gk_ctx *c, int j, int np) {
     for (int p = 0; p < np_total; ++p) {
         const int i = p % j;
         CHK(allreduce(c, slot(c, s0), np));
-        const double *va = V + (i64)i * ld;
+        const T *va = vcol<T>(c, i);
         const int first_pass = p < j;
         if (p + 1 < np_total) {
-            const double *vb = V + (i64)((p + 1) % j) * ld;
-            CHK(proj(c, gk::PJ_AXPY_DOT, c->w, va, vb, slot(c, s0), np, slot(c, s1), hs + i, 1.0, 0, first_pass));
+            const T *vb = vcol<T>(c, (p + 1) % j);
+            CHK(proj<T>(c, gk::PJ_AXPY_DOT, c->w, va, vb, slot(c, s0), np, slot(c, s1), hs + i, 1.0, 0, first_pass));
         } else {
-            CHK(proj(c, gk::PJ_AXPY_NORM, c->w, va, nullptr, slot(c, s0), np, slot(c, s1), hs + i, 1.0, 0,
-                     first_pass));
+            CHK(proj<T>(c, gk::PJ_AXPY_NORM, c->w, va, nullptr, slot(c, s0), np, slot(c, s1), hs + i, 1.0, 0,
+                        first_pass));
         }
         np = c->np_pj;
         std::swap(s0, s1);
     }
     CHK(allreduce(c, slot(c, s0), np));
-    return scale(c, V + (i64)j * ld, c->w, slot(c, s0), np, hs + j, c->hallh_dev + (i64)(j - 1) * m2, hs, j);
+    return scale_col(c, j, slot(c, s0), np, hs + j, c->hallh_dev + (i64)(j - 1) * m2, hs, j);
 }
 
-// mgs_chain on float columns (gk_cb.hpp): the same launches, slots and H slots, with
-// k_proj_cb / k_scale_cb; the closing writes FP32 column j + 1 and vjw.
-int mgs_chain_cb(gk_ctx *c, int j, int np) {
-    const int m2 = c->m + 2;
-    double *hs = c->hall + (i64)(j - 1) * m2;
-    int s0 = 0, s1 = 1;
-    const int np_total = 2 * j;
-    const bool nt = c->tune_nt > 0 || (c->tune_nt < 0 && c->nt_auto);
-    const bool small = (c->nloc / 2 + (i64)c->np_pj * gk::TPB - 1) / ((i64)c->np_pj * gk::TPB) <= 4;  // (launch_proj)
-    for (int p = 0; p < np_total; ++p) {
-        const int i = p % j;
-        CHK(allreduce(c, slot(c, s0), np));
-        const float *vb = p + 1 < np_total ? cb_col(c, (p + 1) % j) : nullptr;
-        {
-            ProfScope ps(c, GK_KID_PROJ);
-            HIPCHK(gk::cb_proj(c->np_pj, nt, small, c->w, cb_col(c, i), vb, slot(c, s0), np, slot(c, s1), hs + i,
-                               c->nloc, p < j ? 1 : 0, c->st));
-        }
-        np = c->np_pj;
-        std::swap(s0, s1);
-    }
-    CHK(allreduce(c, slot(c, s0), np));
-    ProfScope ps(c, GK_KID_SCALE);
-    HIPCHK(gk::cb_scale(c->nblk_stream, cb_col(c, j), cb_vjw(c), nullptr, c->w, slot(c, s0), np, hs + j, c->nloc,
-                        c->hallh_dev + (i64)(j - 1) * m2, hs, j, c->st));
-    return GK_OK;
+int mgs_chain(gk_ctx *c, int j, int np) {
+    return cb_on(c) ? mgs_chain_t<float>(c, j, np) : mgs_chain_t<double>(c, j, np);
 }
 
 // Capture mgs_chain(j) once as a graph (its kernel arguments and communicator
@@ -1222,7 +1209,7 @@ int gk_get_basis(gk_ctx *c, int which, int col, double *out) {
     HIPCHK(hipSetDevice(c->dev));
     const double *src = base + (i64)col * c->ld;
     if (which == 0 && cb_on(c)) {  // the stored float column, widened (exact) through aux
-        HIPCHK(gk::cb_widen(c->nblk_stream, c->aux, cb_col(c, col), c->nloc, c->st));
+        HIPCHK(gk::cb_widen(c->nblk_stream, c->aux, vcol<float>(c, col), c->nloc, c->st));
         src = c->aux;
     }
     HIPCHK(hipMemcpyAsync(out, src, sizeof(double) * c->nloc, hipMemcpyDeviceToHost, c->st));
@@ -1253,7 +1240,8 @@ int gk_set_basis(gk_ctx *c, int col, const double *in) {
     HIPCHK(hipSetDevice(c->dev));
     const size_t nb = sizeof(double) * (size_t)c->nloc;
     if (cb_on(c)) {
-        HIPCHK(hipMemcpyAsync(cb_col(c, col), f.data(), sizeof(float) * (size_t)c->nloc, hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemcpyAsync(vcol<float>(c, col), f.data(), sizeof(float) * (size_t)c->nloc, hipMemcpyHostToDevice,
+                              c->st));
         HIPCHK(hipMemcpyAsync(cb_vjw(c), in, nb, hipMemcpyHostToDevice, c->st));
         if (col == 0) HIPCHK(hipMemcpyAsync(cb_v1w(c), in, nb, hipMemcpyHostToDevice, c->st));
     } else {
@@ -1311,13 +1299,7 @@ int gk_mgs_cycle_start(gk_ctx *c, double *beta) {
     else
         CHK(op_precond(c, c->x, c->w, true, gk::ACC_NORM, nullptr, slot(c, 0)));
     CHK(allreduce(c, slot(c, 0), c->last_np));
-    if (cb_on(c)) {  // FP32 column 1, and widened to v1w (the first dot's partner) and vjw (step 1's input)
-        ProfScope ps(c, GK_KID_SCALE);
-        HIPCHK(gk::cb_scale(c->nblk_stream, cb_col(c, 0), cb_vjw(c), cb_v1w(c), c->w, slot(c, 0), c->last_np, c->hcol,
-                            c->nloc, nullptr, nullptr, 0, c->st));
-    } else {
-        CHK(scale(c, c->V, c->w, slot(c, 0), c->last_np, c->hcol));
-    }
+    CHK(scale_col(c, 0, slot(c, 0), c->last_np, c->hcol));  // FP32 basis: also v1w and vjw, step 1's operands
     CHK(d2h_sync(c, beta, c->hcol, 1));
     c->cycle_mgs = true;
     c->cycle_hh = false;
@@ -1348,19 +1330,16 @@ int gk_mgs_step_async(gk_ctx *c, int j) {
     else
         CHK(op_precond(c, vj, c->w, false, gk::ACC_DOT, v1, slot(c, s0)));
     int np = c->last_np;
-    if (res && cb) {  // ... on float columns (k_mgs_wcb)
-        CHK(cb_step(c, j, cp, slot(c, s0), np, hs, c->hallh_dev + (i64)(j - 1) * m2));
-        HIPCHK(hipEventRecord(c->ev_step[j], c->st));
-        c->prof_on_step = true;
-        return GK_OK;
-    }
     if (res) {  // the whole cascade + norm + scale as one resident launch
         // N ranks on the device exchange: the first dot's rank totals inside the launch
         // (GK_TUNE_RES_FOLD) instead of a k_xchg launch before it
         const bool fold = c->tune_res_fold && c->xs_on && c->nranks > 1;
         if (!fold) CHK(allreduce(c, slot(c, s0), np));
-        CHK(res_step(c, j, rp, slot(c, s0), np, hs, c->hallh_dev + (i64)(j - 1) * m2, gk::RES_MGS, nullptr, -1,
-                     fold ? RESF_PIN_LOCAL : 0));
+        if (cb)  // ... on float columns (k_mgs_wcb; one rank)
+            CHK(cb_step(c, j, cp, slot(c, s0), np, hs, c->hallh_dev + (i64)(j - 1) * m2));
+        else
+            CHK(res_step(c, j, rp, slot(c, s0), np, hs, c->hallh_dev + (i64)(j - 1) * m2, gk::RES_MGS, nullptr, -1,
+                         fold ? RESF_PIN_LOCAL : 0));
         HIPCHK(hipEventRecord(c->ev_step[j], c->st));
         c->prof_on_step = true;
         return GK_OK;
@@ -1429,27 +1408,13 @@ int gk_update_x(gk_ctx *c, const double *y, int n_out) {
     HIPCHK(hipSetDevice(c->dev));
     HIPCHK(hipMemcpyAsync(c->ydev, y, sizeof(double) * n_out, hipMemcpyHostToDevice, c->st));
     if (right_prec(c)) {  // x += M^-1 (V y): t = V y in w, M^-1 t in z
-        {
-            ProfScope ps(c, GK_KID_UPDATE);
-            if (cb_on(c)) {
-                HIPCHK(gk::cb_update_x(c->nblk_stream, false, c->w, cb_base(c), c->ld, c->ydev, n_out, c->nloc, c->st));
-            } else {
-                gk::k_update_x<false><<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->w, c->V, c->ld, c->ydev, n_out, c->nloc);
-                LAUNCHCHK();
-            }
-        }
+        CHK(update_x<false>(c, c->w, n_out));
         CHK(precond_sweeps(c, c->w, c->z, gk::ACC_NONE, nullptr, nullptr));
         ProfScope ps(c, GK_KID_UPDATE);
         gk::k_add<<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->x, c->z, c->nloc);
         LAUNCHCHK();
     } else {
-        ProfScope ps(c, GK_KID_UPDATE);
-        if (cb_on(c)) {
-            HIPCHK(gk::cb_update_x(c->nblk_stream, true, c->x, cb_base(c), c->ld, c->ydev, n_out, c->nloc, c->st));
-        } else {
-            gk::k_update_x<true><<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->x, c->V, c->ld, c->ydev, n_out, c->nloc);
-            LAUNCHCHK();
-        }
+        CHK(update_x<true>(c, c->x, n_out));
     }
     CHK(sync_st(c));
     if (c->prof) CHK(prof_harvest(c));

@@ -1,7 +1,8 @@
 // gk_cb.hip -- the MGS-R step on an FP32-compressed Krylov basis (gk_cb.hpp;
 // gk_set_basis_precision GK_BASIS_F32): the resident step k_mgs_wcb, its planner and
-// launcher, and the float-column forms of the launch path's kernels (projection,
-// scale, x update, widening copy, Gram).
+// launcher, and the two launch-path kernels that exist on float columns only (the scale
+// that writes the column, the widening copy).  The launch path's projection, x update and
+// Gram are the float instantiations of gk_kernels.hpp's k_proj / k_update_x / k_gram.
 //
 // The basis is STORED in FP32; w, every dot, every AXPY, the H column and x stay FP64.
 // A column element is widened exactly on load, and the FP64 expressions and their order
@@ -19,25 +20,7 @@
 
 namespace gk {
 
-typedef float f2v __attribute__((ext_vector_type(2)));
-
-// a float2 of a Krylov column, non-temporal or with the default policy
-template <bool NT>
-__device__ __forceinline__ f2v ldf(const float2 *p) {
-    if constexpr (NT)
-        return __builtin_nontemporal_load(reinterpret_cast<const f2v *>(p));
-    else
-        return *reinterpret_cast<const f2v *>(p);
-}
-
-// The point from which a batch slot's two loaded float2 are used.  Without it the compiler
-// places the widening conversions right behind each load and waits for that load before
-// it issues the next one -- a pass then pays one memory round trip per chunk (measured:
-// 62.7 us per projection at 4096^2 against the FP64 kernel's 29.3); with it the batch's
-// loads go out back to back and the conversions follow the (counted) wait.
-__device__ __forceinline__ void landed(f2v &a, f2v &b) { asm volatile("" : "+v"(a), "+v"(b)); }
-
-// ... and four floats (16 bytes, 16-B aligned) of a column
+// four floats (16 bytes, 16-B aligned) of a column (two: ldf / landed of gk_common.hpp)
 typedef float f4v __attribute__((ext_vector_type(4)));
 template <bool NT>
 __device__ __forceinline__ f4v ldf4(const float2 *p) {
@@ -410,103 +393,6 @@ int cb_launch(const CbPlan &p, const ResArgs &a, float *F, double *vjw, int dev,
     return GK_OK;
 }
 
-// --------------------------------------------------------------------------
-// Launch path: k_proj (PJ_AXPY_DOT / PJ_AXPY_NORM) on float columns -- the same
-// work mapping, prologue and expressions, the columns widened on load.
-// --------------------------------------------------------------------------
-template <bool DOT, bool NT, int U>
-__global__ __launch_bounds__(TPB) void k_proj_cb(double *__restrict__ w, const float *__restrict__ va,
-                                                 const float *__restrict__ vb, const double *__restrict__ pin,
-                                                 int npin, double *__restrict__ pout, double *__restrict__ hslot,
-                                                 i64 n, int hstore) {
-    __shared__ double sm[WAVES];
-    const i64 n2 = n >> 1;
-    double2 *__restrict__ W2 = reinterpret_cast<double2 *>(w);
-    const float2 *__restrict__ A2 = reinterpret_cast<const float2 *>(va);
-    const float2 *__restrict__ B2 = reinterpret_cast<const float2 *>(vb);
-    const i64 hi = n2, step = (i64)gridDim.x * TPB * U;
-    double2 wv[U];
-    f2v av[U], bv[U];
-    i64 idx[U];
-    auto issue = [&](i64 base) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const i64 e = base + (i64)u * TPB;
-            idx[u] = (e < hi) ? e : -1;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const i64 e = idx[u];
-            if (e >= 0) {
-                wv[u] = W2[e];
-                av[u] = ldf<NT>(A2 + e);
-                if (DOT) bv[u] = ldf<NT>(B2 + e);
-            }
-        }
-    };
-    // the first chunk's loads do not depend on h: issued before the slab-reduce prologue
-    i64 base = (i64)blockIdx.x * TPB * U + threadIdx.x;
-    if (base < hi) issue(base);
-    const double h = reduce_slab(pin, npin, sm);
-    // H(i,j) = H(i,j) + h: the first MGS pass starts from H(i,j) = 0
-    if (hslot != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *hslot = (hstore ? 0.0 : *hslot) + h;
-    double acc = 0.0;
-    while (base < hi) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const i64 e = idx[u];
-            if (e >= 0) {
-                landed(av[u], bv[u]);
-                wv[u].x = wv[u].x - h * (double)av[u].x;
-                wv[u].y = wv[u].y - h * (double)av[u].y;
-                W2[e] = wv[u];
-                if (DOT) {
-                    acc = acc + wv[u].x * (double)bv[u].x;
-                    acc = acc + wv[u].y * (double)bv[u].y;
-                } else {
-                    acc = acc + wv[u].x * wv[u].x;
-                    acc = acc + wv[u].y * wv[u].y;
-                }
-            }
-        }
-        base += step;
-        if (base < hi) issue(base);
-    }
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {  // odd-length tail element
-        const i64 e = n - 1;
-        const double x = w[e] - h * (double)va[e];
-        w[e] = x;
-        acc = DOT ? acc + x * (double)vb[e] : acc + x * x;
-    }
-    const double s = block_sum(acc, sm);
-    if (threadIdx.x == 0) pout[blockIdx.x] = s;
-}
-
-template <bool DOT, bool NT>
-static void launch_proj_cb(int blocks, bool small, double *w, const float *va, const float *vb, const double *pin,
-                           int npin, double *pout, double *hslot, i64 n, int hstore, hipStream_t st) {
-    if (small)
-        k_proj_cb<DOT, NT, 4><<<blocks, TPB, 0, st>>>(w, va, vb, pin, npin, pout, hslot, n, hstore);
-    else
-        k_proj_cb<DOT, NT, 2><<<blocks, TPB, 0, st>>>(w, va, vb, pin, npin, pout, hslot, n, hstore);
-}
-
-hipError_t cb_proj(int blocks, bool nt, bool small, double *w, const float *va, const float *vb, const double *pin,
-                   int npin, double *pout, double *hslot, i64 n, int hstore, hipStream_t st) {
-    if (vb != nullptr) {
-        if (nt)
-            launch_proj_cb<true, true>(blocks, small, w, va, vb, pin, npin, pout, hslot, n, hstore, st);
-        else
-            launch_proj_cb<true, false>(blocks, small, w, va, vb, pin, npin, pout, hslot, n, hstore, st);
-    } else {
-        if (nt)
-            launch_proj_cb<false, true>(blocks, small, w, va, vb, pin, npin, pout, hslot, n, hstore, st);
-        else
-            launch_proj_cb<false, false>(blocks, small, w, va, vb, pin, npin, pout, hslot, n, hstore, st);
-    }
-    return hipGetLastError();
-}
-
 // k_scale writing the float column: out = float(w / h), h = sqrt(sum(pin)); the same
 // values widened to vjw and (cycle start: column 1) to v1w.  hslot / hcopy as k_scale.
 __global__ __launch_bounds__(TPB) void k_scale_cb(float *__restrict__ out, double *__restrict__ vjw,
@@ -549,43 +435,6 @@ hipError_t cb_scale(int blocks, float *out, double *vjw, double *v1w, const doub
     return hipGetLastError();
 }
 
-// k_update_x on float columns: x[e] (+)= sum_k F[k*ld + e] * y[k], k sequential
-template <bool ADD>
-__global__ __launch_bounds__(TPB) void k_update_x_cb(double *__restrict__ x, const float *__restrict__ F, i64 ld,
-                                                     const double *__restrict__ y, int nout, i64 n) {
-    const i64 n2 = n >> 1;
-    const i64 stride = (i64)gridDim.x * TPB;
-    double2 *__restrict__ X2 = reinterpret_cast<double2 *>(x);
-    for (i64 e = (i64)blockIdx.x * TPB + threadIdx.x; e < n2; e += stride) {
-        double s0 = 0.0, s1 = 0.0;
-#pragma unroll 8
-        for (int k = 0; k < nout; ++k) {
-            const float2 v = reinterpret_cast<const float2 *>(F + (i64)k * ld)[e];
-            const double yk = y[k];
-            s0 = s0 + (double)v.x * yk;
-            s1 = s1 + (double)v.y * yk;
-        }
-        double2 xv = ADD ? X2[e] : double2{0.0, 0.0};
-        xv.x = ADD ? xv.x + s0 : s0;
-        xv.y = ADD ? xv.y + s1 : s1;
-        X2[e] = xv;
-    }
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        double s = 0.0;
-        for (int k = 0; k < nout; ++k) s = s + (double)F[(i64)k * ld + n - 1] * y[k];
-        x[n - 1] = ADD ? x[n - 1] + s : s;
-    }
-}
-
-hipError_t cb_update_x(int blocks, bool add, double *x, const float *F, i64 ld, const double *y, int nout, i64 n,
-                       hipStream_t st) {
-    if (add)
-        k_update_x_cb<true><<<blocks, TPB, 0, st>>>(x, F, ld, y, nout, n);
-    else
-        k_update_x_cb<false><<<blocks, TPB, 0, st>>>(x, F, ld, y, nout, n);
-    return hipGetLastError();
-}
-
 __global__ __launch_bounds__(TPB) void k_widen_cb(double *__restrict__ out, const float *__restrict__ in, i64 n) {
     const i64 stride = (i64)gridDim.x * TPB;
     for (i64 e = (i64)blockIdx.x * TPB + threadIdx.x; e < n; e += stride) out[e] = (double)in[e];
@@ -596,51 +445,5 @@ hipError_t cb_widen(int blocks, double *out, const float *in, i64 n, hipStream_t
     return hipGetLastError();
 }
 
-// k_gram on float columns (the tree-reduced v_err route): the same tiles, pairs and order
-constexpr int CB_GROWS = 32, CB_GCMAX = 128;
-constexpr int CB_GPPT = (CB_GCMAX * (CB_GCMAX + 1) / 2 + TPB - 1) / TPB;  // pairs per thread
-
-__global__ __launch_bounds__(TPB) void k_gram_cb(const float *__restrict__ F, i64 ld, int c, i64 n,
-                                                 const short2 *__restrict__ pairs, int npairs,
-                                                 double *__restrict__ slab) {
-    __shared__ double tile[CB_GROWS][CB_GCMAX + 1];
-    double acc[CB_GPPT];
-#pragma unroll
-    for (int q = 0; q < CB_GPPT; ++q) acc[q] = 0.0;
-    const i64 nchunks = (n + CB_GROWS - 1) / CB_GROWS;
-    for (i64 ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
-        const i64 r0 = ch * CB_GROWS;
-        for (int t = threadIdx.x; t < CB_GROWS * c; t += TPB) {
-            const int col = t / CB_GROWS, r = t % CB_GROWS;
-            const i64 e = r0 + r;
-            tile[r][col] = (e < n) ? (double)F[(i64)col * ld + e] : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < CB_GPPT; ++q) {
-            const int p = threadIdx.x + q * TPB;
-            if (p < npairs) {
-                const short2 ab = pairs[p];
-                double s = 0.0;
-#pragma unroll 8
-                for (int r = 0; r < CB_GROWS; ++r) s = s + tile[r][ab.x] * tile[r][ab.y];
-                acc[q] = acc[q] + s;
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < CB_GPPT; ++q) {
-        const int p = threadIdx.x + q * TPB;
-        if (p < npairs) slab[(i64)blockIdx.x * npairs + p] = acc[q];
-    }
-}
-
-hipError_t cb_gram(int blocks, const float *F, i64 ld, int c, i64 n, const short2 *pairs, int npairs, double *slab,
-                   hipStream_t st) {
-    if (c > CB_GCMAX) return hipErrorInvalidValue;
-    k_gram_cb<<<blocks, TPB, 0, st>>>(F, ld, c, n, pairs, npairs, slab);
-    return hipGetLastError();
-}
-
 }  // namespace gk
+

@@ -50,22 +50,13 @@ GK_HIDDEN void cb_plan_info(const CbPlan &p, long long *info);
 GK_HIDDEN int cb_launch(const CbPlan &p, const ResArgs &a, float *F, double *vjw, int dev, hipStream_t st,
                         std::string &msg);
 
-// Launch path on float columns (each returns hipGetLastError() of its launch).
-// w -= h va, h = sum(pin); then the partial slab of <w, vb> (vb != nullptr) or <w, w>
-GK_HIDDEN hipError_t cb_proj(int blocks, bool nt, bool small, double *w, const float *va, const float *vb,
-                             const double *pin, int npin, double *pout, double *hslot, i64 n, int hstore,
-                             hipStream_t st);
+// The launch path's two kernels of float columns alone (each returns hipGetLastError() of
+// its launch; projection, x update and Gram: k_proj / k_update_x / k_gram<float>, gk_kernels.hpp).
 // out = float(w / h), h = sqrt(sum(pin)), the same values widened to vjw (and to v1w unless nullptr)
 GK_HIDDEN hipError_t cb_scale(int blocks, float *out, double *vjw, double *v1w, const double *w, const double *pin,
                               int npin, double *hslot, i64 n, double *hcopy, const double *hsrc, int ncopy,
                               hipStream_t st);
-// x (+)= sum_k F(:,k) y(k)
-GK_HIDDEN hipError_t cb_update_x(int blocks, bool add, double *x, const float *F, i64 ld, const double *y, int nout,
-                                 i64 n, hipStream_t st);
 // out = in widened
 GK_HIDDEN hipError_t cb_widen(int blocks, double *out, const float *in, i64 n, hipStream_t st);
-// k_gram on float columns: slab[blk * npairs + p]
-GK_HIDDEN hipError_t cb_gram(int blocks, const float *F, i64 ld, int c, i64 n, const short2 *pairs, int npairs,
-                             double *slab, hipStream_t st);
 
 }  // namespace gk

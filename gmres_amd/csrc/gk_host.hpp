@@ -210,8 +210,8 @@ inline bool right_prec(const gk_ctx *c) { return c->side == GK_SIDE_RIGHT && c->
 // Compressed basis (gk_cb.hpp): the FP32 columns in the lower half of V, the two widened
 // FP64 vectors the operator stage reads in its last two double columns.
 inline bool cb_on(const gk_ctx *c) { return c->basis == GK_BASIS_F32; }
-inline float *cb_base(const gk_ctx *c) { return reinterpret_cast<float *>(c->V); }
-inline float *cb_col(const gk_ctx *c, int k) { return cb_base(c) + (i64)k * c->ld; }
+template <class T>  // column k (0-based) of the MGS-R basis in the type T it is stored in
+inline T *vcol(const gk_ctx *c, int k) { return reinterpret_cast<T *>(c->V) + (i64)k * c->ld; }
 inline double *cb_v1w(const gk_ctx *c) { return c->V + (i64)(c->m - 1) * c->ld; }
 inline double *cb_vjw(const gk_ctx *c) { return c->V + (i64)c->m * c->ld; }
 

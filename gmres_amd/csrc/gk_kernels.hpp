@@ -34,13 +34,17 @@ namespace gk {
 // One launch = one AXPY of projection i fused with the dot of projection i+1:
 // reads w, va, vb and writes w (32 B/unknown) where the reference's separate
 // dot + AXPY move 40 B/unknown.
+//
+// T = float: va / vb are columns of the FP32-stored basis (gk_cb.hpp), widened exactly
+// on load -- 24 B/unknown; w, h, the dot and every expression stay FP64.  Only
+// PJ_AXPY_DOT / PJ_AXPY_NORM are instantiated, and `coef` / `blocked` / `tail0` are compiled
+// out (the MGS-R chain is all float columns ever had: coef 1, grid-stride, no tail0).
 // --------------------------------------------------------------------------
 enum { PJ_DOT = 0, PJ_AXPY = 1, PJ_AXPY_DOT = 2, PJ_AXPY_NORM = 3 };
 
-
-template <int MODE, bool NT = false, int U = UNR>
-__global__ __launch_bounds__(TPB) void k_proj(double *__restrict__ w, const double *__restrict__ va,
-                                              const double *__restrict__ vb,
+template <int MODE, bool NT = false, int U = UNR, class T = double>
+__global__ __launch_bounds__(TPB) void k_proj(double *__restrict__ w, const T *__restrict__ va,
+                                              const T *__restrict__ vb,
                                               const double *__restrict__ pin, int npin,
                                               double *__restrict__ pout, double *__restrict__ hslot,
                                               double coef, i64 n, i64 tail0, int blocked,
@@ -48,15 +52,18 @@ __global__ __launch_bounds__(TPB) void k_proj(double *__restrict__ w, const doub
     __shared__ double sm[WAVES];
     const i64 n2 = n >> 1;
     double2 *__restrict__ W2 = reinterpret_cast<double2 *>(w);
-    const double2 *__restrict__ A2 = reinterpret_cast<const double2 *>(va);
-    const double2 *__restrict__ B2 = reinterpret_cast<const double2 *>(vb);
+    typedef Col<T> C;
+    constexpr bool F64 = std::is_same<T, double>::value;
+    static_assert(F64 || MODE == PJ_AXPY_DOT || MODE == PJ_AXPY_NORM, "float columns: the MGS-R chain's two forms");
+    const typename C::m2 *__restrict__ A2 = reinterpret_cast<const typename C::m2 *>(va);
+    const typename C::m2 *__restrict__ B2 = reinterpret_cast<const typename C::m2 *>(vb);
     // Work mapping: grid-stride over U*TPB double2 chunks; `blocked` (one contiguous
     // range per workgroup) is always 0 since GK_TUNE_PROJ_BLOCKED was retired.  The
     // argument and its branch stay for now: the kernel without them ran the
     // launch-per-projection path 3 % slower at 4096^2 (138.9-139.4 vs 143.0-144.6 it/s,
     // three interleaved pairs), so this is still the machine code that was tuned.
     i64 lo, hi, step;
-    if (blocked) {
+    if (F64 && blocked) {
         const i64 chunk = (i64)TPB * U;
         const i64 per = ((n2 + gridDim.x - 1) / gridDim.x + chunk - 1) / chunk * chunk;
         lo = (i64)blockIdx.x * per;
@@ -67,7 +74,8 @@ __global__ __launch_bounds__(TPB) void k_proj(double *__restrict__ w, const doub
         hi = n2;
         step = (i64)gridDim.x * TPB * U;
     }
-    double2 wv[U], av[U], bv[U];
+    double2 wv[U];
+    typename C::v2 av[U], bv[U];
     i64 idx[U];
     auto issue = [&](i64 base) {
 #pragma unroll
@@ -80,8 +88,8 @@ __global__ __launch_bounds__(TPB) void k_proj(double *__restrict__ w, const doub
             const i64 e = idx[u];
             if (e >= 0) {
                 wv[u] = W2[e];
-                if (MODE != PJ_DOT) av[u] = ldv<NT>(A2 + e);
-                if (MODE == PJ_DOT || MODE == PJ_AXPY_DOT) bv[u] = ldv<NT>(B2 + e);
+                if (MODE != PJ_DOT) av[u] = C::template ld<NT>(A2 + e);
+                if (MODE == PJ_DOT || MODE == PJ_AXPY_DOT) bv[u] = C::template ld<NT>(B2 + e);
             }
         }
     };
@@ -95,7 +103,7 @@ __global__ __launch_bounds__(TPB) void k_proj(double *__restrict__ w, const doub
         const double h = reduce_slab(pin, npin, sm);
         // H(i,j) = H(i,j) + h: the first MGS pass starts from H(i,j) = 0
         if (hslot != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *hslot = (hstore ? 0.0 : *hslot) + h;
-        ch = coef * h;
+        ch = F64 ? coef * h : h;
     }
     double acc = 0.0;
     while (base < hi) {
@@ -103,18 +111,19 @@ __global__ __launch_bounds__(TPB) void k_proj(double *__restrict__ w, const doub
         for (int u = 0; u < U; ++u) {
             const i64 e = idx[u];
             if (e >= 0) {
+                C::landed(av[u], bv[u]);
                 if (MODE != PJ_DOT) {
-                    wv[u].x = wv[u].x - ch * av[u].x;
-                    wv[u].y = wv[u].y - ch * av[u].y;
+                    wv[u].x = wv[u].x - ch * (double)av[u].x;
+                    wv[u].y = wv[u].y - ch * (double)av[u].y;
                     W2[e] = wv[u];
                 }
                 if (MODE == PJ_DOT || MODE == PJ_AXPY_DOT) {
-                    acc = acc + wv[u].x * bv[u].x;
-                    acc = acc + wv[u].y * bv[u].y;
+                    acc = acc + wv[u].x * (double)bv[u].x;
+                    acc = acc + wv[u].y * (double)bv[u].y;
                 }
                 if (MODE == PJ_AXPY_NORM) {
-                    if (2 * e >= tail0) acc = acc + wv[u].x * wv[u].x;
-                    if (2 * e + 1 >= tail0) acc = acc + wv[u].y * wv[u].y;
+                    if (!F64 || 2 * e >= tail0) acc = acc + wv[u].x * wv[u].x;
+                    if (!F64 || 2 * e + 1 >= tail0) acc = acc + wv[u].y * wv[u].y;
                 }
             }
         }
@@ -125,11 +134,11 @@ __global__ __launch_bounds__(TPB) void k_proj(double *__restrict__ w, const doub
         const i64 e = n - 1;
         double x = w[e];
         if (MODE != PJ_DOT) {
-            x = x - ch * va[e];
+            x = x - ch * (double)va[e];
             w[e] = x;
         }
-        if (MODE == PJ_DOT || MODE == PJ_AXPY_DOT) acc = acc + x * vb[e];
-        if (MODE == PJ_AXPY_NORM && e >= tail0) acc = acc + x * x;
+        if (MODE == PJ_DOT || MODE == PJ_AXPY_DOT) acc = acc + x * (double)vb[e];
+        if (MODE == PJ_AXPY_NORM && (!F64 || e >= tail0)) acc = acc + x * x;
     }
     if (MODE != PJ_AXPY) {
         const double s = block_sum(acc, sm);
@@ -220,8 +229,9 @@ __global__ __launch_bounds__(TPB) void k_finalize(const double *__restrict__ pin
 // x[e] += sum_k V[k*ld + e] * y[k]  (gmres_mgsr.f90:400-406: the reference's
 // row-wise dot_product(V(idx,1:n_out), y) with idx on the lane, k sequential).
 // ADD = false: x[e] = that sum (t = V y of the right-preconditioned update).
-template <bool ADD = true>
-__global__ __launch_bounds__(TPB) void k_update_x(double *__restrict__ x, const double *__restrict__ V,
+// T: the type the columns are stored in (float: widened exactly on load).
+template <bool ADD = true, class T = double>
+__global__ __launch_bounds__(TPB) void k_update_x(double *__restrict__ x, const T *__restrict__ V,
                                                   i64 ld, const double *__restrict__ y, int nout, i64 n) {
     const i64 n2 = n >> 1;
     const i64 stride = (i64)gridDim.x * TPB;
@@ -230,10 +240,10 @@ __global__ __launch_bounds__(TPB) void k_update_x(double *__restrict__ x, const 
         double s0 = 0.0, s1 = 0.0;
 #pragma unroll 8
         for (int k = 0; k < nout; ++k) {
-            const double2 v = reinterpret_cast<const double2 *>(V + (i64)k * ld)[e];
+            const typename Col<T>::m2 v = reinterpret_cast<const typename Col<T>::m2 *>(V + (i64)k * ld)[e];
             const double yk = y[k];
-            s0 = s0 + v.x * yk;
-            s1 = s1 + v.y * yk;
+            s0 = s0 + (double)v.x * yk;
+            s1 = s1 + (double)v.y * yk;
         }
         double2 xv = ADD ? X2[e] : double2{0.0, 0.0};
         xv.x = ADD ? xv.x + s0 : s0;
@@ -242,7 +252,7 @@ __global__ __launch_bounds__(TPB) void k_update_x(double *__restrict__ x, const 
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         double s = 0.0;
-        for (int k = 0; k < nout; ++k) s = s + V[(i64)k * ld + n - 1] * y[k];
+        for (int k = 0; k < nout; ++k) s = s + (double)V[(i64)k * ld + n - 1] * y[k];
         x[n - 1] = ADD ? x[n - 1] + s : s;
     }
 }
@@ -704,13 +714,14 @@ __global__ __launch_bounds__(TPB) void k_right_cbpr2(RcArgs a) {
 // gmres_mgsr.f90:414-420, gmres_hh.f90:587-591).  Off the Arnoldi metric.
 // Each workgroup stages GROWS rows x c columns in LDS and accumulates the
 // c(c+1)/2 pairs it owns; slab[blk*npairs + p]; then k_gram_reduce sums the
-// slab over workgroups in a fixed order.
+// slab over workgroups in a fixed order.  T: the type the columns are stored in.
 // --------------------------------------------------------------------------
 constexpr int GROWS = 32;
 constexpr int GCMAX = 128;
 constexpr int GPPT = (GCMAX * (GCMAX + 1) / 2 + TPB - 1) / TPB;  // pairs per thread
 
-__global__ __launch_bounds__(TPB) void k_gram(const double *__restrict__ V, i64 ld, int c, i64 n,
+template <class T = double>
+__global__ __launch_bounds__(TPB) void k_gram(const T *__restrict__ V, i64 ld, int c, i64 n,
                                               const short2 *__restrict__ pairs, int npairs,
                                               double *__restrict__ slab) {
     __shared__ double tile[GROWS][GCMAX + 1];
@@ -723,7 +734,7 @@ __global__ __launch_bounds__(TPB) void k_gram(const double *__restrict__ V, i64 
         for (int t = threadIdx.x; t < GROWS * c; t += TPB) {
             const int col = t / GROWS, r = t % GROWS;
             const i64 e = r0 + r;
-            tile[r][col] = (e < n) ? V[(i64)col * ld + e] : 0.0;
+            tile[r][col] = (e < n) ? (double)V[(i64)col * ld + e] : 0.0;
         }
         __syncthreads();
 #pragma unroll

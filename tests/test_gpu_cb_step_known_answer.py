@@ -124,7 +124,7 @@ LAUNCH_CASES = ([(N, m, 0, nt) for N, m in CB_LAUNCH_SHAPES for nt in (1, 0)]
 @pytest.mark.parametrize("graph", [0, 1])
 @pytest.mark.parametrize("N,m,blocks,nt", LAUNCH_CASES)
 def test_launch_path_step(oracle, N, m, blocks, nt, graph):
-    """k_proj_cb / k_scale_cb (GK_TUNE_RES 0), call by call and as a hipGraph (every graph step
+    """k_proj<..., float> / k_scale_cb (GK_TUNE_RES 0), call by call and as a hipGraph (every graph step
     twice: the second is a replay), non-temporal column loads and not; j = 1, 2, m.
     GK_TUNE_PROJ_BLOCKS 3: at 130^2 the U = 2 form, six trips of the grid-stride loop with a
     ragged last one; at 45^2 (1012 double2: any block count leaves at most four per thread) the
@@ -234,11 +234,11 @@ def test_update_x_on_planted_columns(oracle, route, side, prec):
     through set_x, which separates the accumulator from the product.
 
     Left, and right with the identity (right_prec is false there: the same launch as left):
-    k_update_x_cb<ADD> forms x + V y; the bound is 64 eps sum_k |y_k V_k| =: 64 eps mag per
+    k_update_x<ADD, float> forms x + V y; the bound is 64 eps sum_k |y_k V_k| =: 64 eps mag per
     element, and the planted x is u mag with |u| <= 1, so that the closing addition rounds
     within eps mag and the bound needs no term of its own for x.
 
-    Right with cbpr2: the other form, k_update_x_cb<false> writes t = V y into w, then
+    Right with cbpr2: the other form, k_update_x<false, float> writes t = V y into w, then
     x += M^-1 t (cbpr2 sweep + k_add; the profile must show the sweep and two update launches
     per call).  w has no vector id, so x is held, against x + M^-1 (V y) with
     cbpr2 in long double.  Bound: 64 eps |M^-1| mag with |M^-1| u = u / d + |alpha| (u + |A| u / d)
@@ -276,7 +276,7 @@ def test_update_x_on_planted_columns(oracle, route, side, prec):
                 assert not np.array_equal(x, x0)
         prof = c.profile_read()
     print(f"update_x N={N} {side} {prec}: update launches {prof['update'][1]}, cbpr2 sweeps {prof['stencil'][1]}")
-    if right:  # per call: k_update_x_cb<false>, the cbpr2 sweep (profiled with the stencil launches), k_add
+    if right:  # per call: k_update_x<false, float>, the cbpr2 sweep (profiled with the stencil launches), k_add
         assert prof["update"][1] == 8 and prof["stencil"][1] == 4, prof
     else:
         assert prof["update"][1] == 4 and prof["stencil"][1] == 0, prof
@@ -300,7 +300,7 @@ def _verr_ref(V, n_out, zero_last):
 
 @pytest.mark.parametrize("route", VEC_ROUTES, ids=[r[0] for r in VEC_ROUTES])
 def test_mgs_verr_on_planted_columns(route):
-    """k_gram_cb on Gram entries ~1e-5: v_err to 1e-10 relative of the exact-dot evaluation,
+    """k_gram<float> on Gram entries ~1e-5: v_err to 1e-10 relative of the exact-dot evaluation,
     with and without the zeroed last column; GK_TUNE_VERR_ORDER 1 and 0 give the same bits
     (the float route is the tree either way)."""
     _, N, m, tunes = route
@@ -324,7 +324,7 @@ def test_mgs_verr_on_planted_columns(route):
 
 
 def test_mgs_verr_at_the_column_limit():
-    """n_out + 1 = 128 columns (CB_GCMAX: every pair slot of k_gram_cb's tile) at 45^2, and
+    """n_out + 1 = 128 columns (GCMAX: every pair slot of k_gram<float>'s tile) at 45^2, and
     129 columns, which must be refused (GK_ERR_ARG) before anything is launched."""
     from gmres_amd import _native as nat
 
