@@ -6,8 +6,10 @@
 
 #include <atomic>
 
+#include "../../include/gmres_hip.h"
 #include "gk_blk.hpp"
 #include "gk_res.hpp"
+#include "gk_resident.hpp"
 
 namespace gk {
 
@@ -423,7 +425,8 @@ __global__ __launch_bounds__(NT, 1) void k_mgs_blk(ResArgs a) {
         if (wv < K && lane == 0) atomicAdd(&xdone, 1);
         if constexpr (TCH > 0) {
             // the first TCH chunks of the following pass's last dot column, one dword per
-            // 128-B line, paced, until every all-gather wave holds its total
+            // 128-B line, paced, until every all-gather wave holds its total (res_touch of
+            // gk_res.hpp with a count of waves for its stop test; kept apart: see there)
             const int kw = K < NW ? K : NW;
             if (wv >= kw && p + 2 < P) {
                 const int b2 = blk_of(p + 2);
@@ -480,30 +483,19 @@ __global__ __launch_bounds__(NT, 1) void k_mgs_blk(ResArgs a) {
     if (!ok) return;  // uniform per workgroup; *err is set
     const double hn = sqrt(bc[0]);
     double2 *__restrict__ O2 = reinterpret_cast<double2 *>(a.vout);
-    auto outv = [&](const double2 &v) { return hn != 0.0 ? double2{v.x / hn, v.y / hn} : double2{0.0, 0.0}; };
     {
         int cb, ce;
         range(cb, ce);
 #pragma unroll
         for (int k = 0; k < RW; ++k)
-            if (cb + k < ce) O2[(i64)(cb + k) * NT + t] = outv(wr[k]);
+            if (cb + k < ce) O2[(i64)(cb + k) * NT + t] = res_unit(wr[k], hn);
     }
     for (int k = 0; k < LW; ++k)
-        if (l0 + k < lend) O2[(l0 + k) * NT + t] = outv(lw[k * NT + t]);
-    for (i64 e = a.nres2 + (i64)res_stream_wg() * NT + t; e < n2; e += sstride) O2[e] = outv(W2[e]);
-    if ((a.n & 1) && blockIdx.x == gridDim.x - 1 && t == 0) a.vout[a.n - 1] = hn != 0.0 ? a.w[a.n - 1] / hn : 0.0;
+        if (l0 + k < lend) O2[(l0 + k) * NT + t] = res_unit(lw[k * NT + t], hn);
+    for (i64 e = a.nres2 + (i64)res_stream_wg() * NT + t; e < n2; e += sstride) O2[e] = res_unit(W2[e], hn);
+    if ((a.n & 1) && blockIdx.x == gridDim.x - 1 && t == 0) a.vout[a.n - 1] = res_unit(a.w + a.n - 1, hn);
     clk.finish(a.stamps, RES_MGS);
-    if (blockIdx.x == 0) {
-        __syncthreads();
-        for (int k = t; k < j; k += NT) {
-            a.hs[k] = hsh[k];
-            a.hcopy[k] = hsh[k];
-        }
-        if (t == 0) {
-            a.hs[j] = hn;
-            a.hcopy[j] = hn;
-        }
-    }
+    res_store_hcol<NT>(a, hsh, j, hn);
 }
 
 // ------------------------------------------------------------------ host ---
@@ -570,28 +562,32 @@ struct BlkCfg<4> {
     static constexpr int wb[BLK_NVAR] = {4, 4, 2, 1, 2};
 };
 
+int no_kernel(int var, int S, std::string &msg) {
+    return fail(msg, GK_ERR_HIP, "k_mgs_blk: no instantiation for S=%d, variant %d", S, var);
+}
+
 template <int S, int V>
-int launch_v(const ResArgs &a, int G, int lds, int dev, hipStream_t st) {
+int launch_v(const ResArgs &a, int G, int lds, int dev, hipStream_t st, std::string &msg) {
     constexpr BlkGeom g = BlkCfg<S>::g[V];
     constexpr int WBT = BlkCfg<S>::wb[V];
     constexpr int TCH = V == BLK_WONLY ? BLK_TOUCH : 0;
     auto kern = &k_mgs_blk<g.rw, g.lw, g.rx, g.lx, S, WBT, TCH, g.nt, g.pfx>;
     static std::atomic<int> attr[ATTR_DEVS];
-    const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void *>(kern), dev, lds, attr);
-    if (e != hipSuccess) return (int)e;
+    const int e = dyn_lds(reinterpret_cast<const void *>(kern), dev, lds, attr, msg);
+    if (e != GK_OK) return e;
     kern<<<G, g.nt, lds, st>>>(a);
-    return (int)hipGetLastError();
+    return launched("blocked step", msg);
 }
 
 template <int S>
-int launch_s(int var, const ResArgs &a, int G, int lds, int dev, hipStream_t st) {
+int launch_s(int var, const ResArgs &a, int G, int lds, int dev, hipStream_t st, std::string &msg) {
     switch (var) {
-        case BLK_R4: return launch_v<S, BLK_R4>(a, G, lds, dev, st);
-        case BLK_R8: return launch_v<S, BLK_R8>(a, G, lds, dev, st);
-        case BLK_R16: return launch_v<S, BLK_R16>(a, G, lds, dev, st);
-        case BLK_R32: return launch_v<S, BLK_R32>(a, G, lds, dev, st);
-        case BLK_WONLY: return launch_v<S, BLK_WONLY>(a, G, lds, dev, st);
-        default: return (int)hipErrorInvalidValue;
+        case BLK_R4: return launch_v<S, BLK_R4>(a, G, lds, dev, st, msg);
+        case BLK_R8: return launch_v<S, BLK_R8>(a, G, lds, dev, st, msg);
+        case BLK_R16: return launch_v<S, BLK_R16>(a, G, lds, dev, st, msg);
+        case BLK_R32: return launch_v<S, BLK_R32>(a, G, lds, dev, st, msg);
+        case BLK_WONLY: return launch_v<S, BLK_WONLY>(a, G, lds, dev, st, msg);
+        default: return no_kernel(var, S, msg);
     }
 }
 
@@ -606,12 +602,12 @@ int blk_variant(long long chunks512) {
     return chunks512 <= 4 ? BLK_R4 : chunks512 <= 8 ? BLK_R8 : chunks512 <= 16 ? BLK_R16 : chunks512 <= 32 ? BLK_R32 : BLK_WONLY;
 }
 
-int blk_launch(int var, int S, const ResArgs &a, int G, int lds, int dev, hipStream_t st) {
+int blk_launch(int var, int S, const ResArgs &a, int G, int lds, int dev, hipStream_t st, std::string &msg) {
     switch (S) {
-        case 1: return var == BLK_WONLY ? (int)hipErrorInvalidValue : launch_s<1>(var, a, G, lds, dev, st);
-        case 2: return launch_s<2>(var, a, G, lds, dev, st);
-        case 4: return launch_s<4>(var, a, G, lds, dev, st);
-        default: return (int)hipErrorInvalidValue;
+        case 1: return var == BLK_WONLY ? no_kernel(var, S, msg) : launch_s<1>(var, a, G, lds, dev, st, msg);
+        case 2: return launch_s<2>(var, a, G, lds, dev, st, msg);
+        case 4: return launch_s<4>(var, a, G, lds, dev, st, msg);
+        default: return no_kernel(var, S, msg);
     }
 }
 

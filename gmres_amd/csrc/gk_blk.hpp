@@ -21,6 +21,8 @@
 // V_j carries <V_{c_l}, V_j> as extra values of its all-gather; the others come
 // from the cycle's Gram table (ResArgs::gm, written by workgroup 0).
 #pragma once
+#include <string>
+
 #include "gk_common.hpp"
 
 namespace gk {
@@ -42,8 +44,8 @@ BlkGeom blk_geom(int var, int S);
 int blk_variant(long long chunks512);  // chunks per thread at 512 threads; BLK_WONLY past 32
 
 // Launch step j's blocked MGS-R launch: G workgroups of blk_geom(var, S).nt threads,
-// `lds` bytes of dynamic LDS; returns a hipError_t (hipErrorInvalidValue for an
-// unsupported S / variant).
-int blk_launch(int var, int S, const ResArgs &a, int G, int lds, int dev, hipStream_t st);
+// `lds` bytes of dynamic LDS; returns GK_OK, or a GK_ERR_* code with its text in msg (an
+// unsupported S / variant among them).
+int blk_launch(int var, int S, const ResArgs &a, int G, int lds, int dev, hipStream_t st, std::string &msg);
 
 }  // namespace gk

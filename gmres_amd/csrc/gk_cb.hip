@@ -11,12 +11,11 @@
 // 0 when h = 0; the same value widened goes to vjw, which the operator stage reads.
 // A projection then moves 8 B per unknown of the resident part instead of 16.
 #include <algorithm>
-#include <cstdarg>
-#include <cstdio>
 
 #include "../../include/gmres_hip.h"
 #include "gk_cb.hpp"
 #include "gk_res.hpp"
+#include "gk_resident.hpp"
 
 namespace gk {
 
@@ -31,7 +30,8 @@ __device__ __forceinline__ f4v ldf4(const float2 *p) {
 }
 __device__ __forceinline__ void landed(f4v &a, f4v &b) { asm volatile("" : "+v"(a), "+v"(b)); }
 
-// the stored form of one new column element and what every later reader sees of it
+// the stored form of one new column element and what every later reader sees of it: res_unit
+// (gk_res.hpp, which states the zero-norm rule) rounded once to FP32
 __device__ __forceinline__ float cb_round(double w, double h) { return h != 0.0 ? (float)(w / h) : 0.0f; }
 
 // --------------------------------------------------------------------------
@@ -251,14 +251,7 @@ __global__ __launch_bounds__(CB_WT, 1) void k_mgs_wcb(CbArgs ca) {
             const i64 nc = cend - c0;
             const i64 lines = (i64)16 * (nc < TCH ? (nc > 0 ? nc : 0) : TCH);
             const char *base = reinterpret_cast<const char *>(F2 + (i64)touch_col * ld2 + c0 * WT);
-            for (i64 l = t - 64; l < lines; l += WT - 64) {
-                if constexpr (PACE > 0) {
-                    if (*(volatile int *)&xdone) break;  // wave-uniform: one LDS word
-                }
-                const char *ptr = base + l * 128;
-                asm volatile("global_load_dword %0, %1, off" : "+v"(touch_sink) : "v"(ptr) : "memory");
-                if constexpr (PACE > 0) __builtin_amdgcn_s_sleep(PACE);
-            }
+            res_touch<PACE>(base, lines, t - 64, WT - 64, &xdone, touch_sink);
         }
         __syncthreads();
         if constexpr (TCH > 0) asm volatile("s_waitcnt vmcnt(0)" : : "v"(touch_sink) : "memory");
@@ -310,17 +303,7 @@ __global__ __launch_bounds__(CB_WT, 1) void k_mgs_wcb(CbArgs ca) {
         ca.vjw[a.n - 1] = (double)f;
     }
     clk.finish(a.stamps, RES_MGS);
-    if (blockIdx.x == 0) {
-        __syncthreads();
-        for (int k = t; k < j; k += WT) {
-            a.hs[k] = hsh[k];
-            a.hcopy[k] = hsh[k];
-        }
-        if (t == 0) {
-            a.hs[j] = hn;
-            a.hcopy[j] = hn;
-        }
-    }
+    res_store_hcol<WT>(a, hsh, j, hn);
 }
 
 // static LDS of k_mgs_wcb: sm, bc, okf, xdone, hsh
@@ -333,13 +316,8 @@ static_assert(CB_LDS_DYN > 80 * 1024, "k_mgs_wcb: the dynamic LDS must pin one w
 void plan_cb(i64 nloc, int cus, int share, int m, CbPlan &p) {
     p = CbPlan{};
     p.G = std::max(1, std::min(RGMAX, cus / std::max(1, share)));
-    const i64 n2 = nloc / 2, nchf = n2 / CB_WT, G = p.G;
-    // the resident chunks spread evenly: every workgroup ceil(chunks / G) register chunks
-    // (at most CB_RW), then the same for LDS (plan_resident's spread)
-    p.r2e = (int)std::min<i64>(CB_RW, (nchf + G - 1) / G);
-    const i64 rest = std::max<i64>(0, nchf - G * p.r2e);
-    p.l2e = (int)std::min<i64>(CB_LW, (rest + G - 1) / G);
-    p.nres2 = std::min<i64>(nchf, G * (p.r2e + p.l2e)) * CB_WT;
+    const i64 n2 = nloc / 2;
+    res_spread(n2, CB_WT, p.G, CB_RW, CB_LW, p.r2e, p.l2e, p.nres2);
     p.nstream2 = n2 - p.nres2;
     p.lds = CB_LDS_DYN;
     p.on = m + 1 <= WO_HMAX;  // the H column: WO_HMAX entries of LDS
@@ -359,38 +337,22 @@ void cb_plan_info(const CbPlan &p, long long *info) {
 }
 
 // --------------------------------------------------------------- launcher ---
-static int cb_fail(std::string &msg, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    msg = buf;
-    return code;
-}
-
 int cb_launch(const CbPlan &p, const ResArgs &a, float *F, double *vjw, int dev, hipStream_t st, std::string &msg) {
     if (!p.on || p.r2e > CB_RW || p.l2e > CB_LW || p.G < 1 || p.G > RGMAX || a.j < 1 || a.j + 1 > WO_HMAX ||
         a.nres2 != p.nres2 || a.nranks != 1 || (a.nres2 % CB_WT) != 0 || a.nres2 > a.n / 2 ||
         a.nres2 > (i64)p.G * (p.r2e + p.l2e) * CB_WT)
-        return cb_fail(msg, GK_ERR_STATE, "compressed-basis step: plan (%d + %d chunks on %d workgroups) does not fit", p.r2e,
-                       p.l2e, p.G);
+        return fail(msg, GK_ERR_STATE, "compressed-basis step: plan (%d + %d chunks on %d workgroups) does not fit", p.r2e,
+                    p.l2e, p.G);
     static std::atomic<int> attr[ATTR_DEVS];
-    const void *kern = reinterpret_cast<const void *>(&k_mgs_wcb<CB_RW, CB_LW, CB_WB>);
-    if (dev < 0 || dev >= ATTR_DEVS) return cb_fail(msg, GK_ERR_ARG, "device id %d out of range", dev);
-    hipError_t e = ensure_dyn_lds(kern, dev, p.lds, attr);
-    if (e != hipSuccess)
-        return cb_fail(msg, GK_ERR_HIP, "%s:%d hipFuncSetAttribute(dynamic LDS %d): %s", __FILE__, __LINE__, p.lds,
-                       hipGetErrorString(e));
+    const int e = dyn_lds(reinterpret_cast<const void *>(&k_mgs_wcb<CB_RW, CB_LW, CB_WB>), dev, p.lds, attr, msg);
+    if (e != GK_OK) return e;
     CbArgs ca{};
     ca.r = a;
     ca.F = F;
     ca.fout = F + (i64)a.j * a.ld;
     ca.vjw = vjw;
     k_mgs_wcb<CB_RW, CB_LW, CB_WB><<<p.G, CB_WT, p.lds, st>>>(ca);
-    e = hipGetLastError();
-    if (e != hipSuccess) return cb_fail(msg, GK_ERR_HIP, "compressed-basis step launch: %s", hipGetErrorString(e));
-    return GK_OK;
+    return launched("compressed-basis step", msg);
 }
 
 // k_scale writing the float column: out = float(w / h), h = sqrt(sum(pin)); the same

@@ -1,6 +1,7 @@
 // gk_res.hpp -- device-side machinery shared by the resident MGS-R / Householder
-// step kernels (gk_resident.hip, gk_blk.hip): the device-exchange granule
-// primitives, ResArgs and the in-launch all-gather.  Only inline functions,
+// step kernels (gk_resident.hip, gk_blk.hip, gk_cb.hip): the device-exchange granule
+// primitives, ResArgs, the in-launch all-gather and the closing stages the kernels
+// share (res_unit, res_store_hcol, res_touch).  Only inline functions,
 // constants and types: included by more than one translation unit.
 #pragma once
 #include "gk_common.hpp"
@@ -231,6 +232,62 @@ __device__ __forceinline__ double block_sum_rt(double v, double *sm) {
     for (int k = 1; k < RWAVES; ++k) r += sm[k];
     __syncthreads();  // sm is rewritten next
     return r;
+}
+
+// --------------------------------------------------------------------------
+// Stages of the protocol around a pass, the same in all five resident kernels
+// (k_mgs_res / k_mgs_wres / k_mgs_wpc, k_mgs_blk, k_mgs_wcb); what differs
+// between the kernels is the pass.  Shared here: the unit scale (res_unit), the
+// H column write-out (res_store_hcol), the L2 touch (res_touch) -- each leaves
+// every kernel's instruction stream as it was.  Still written out in each kernel,
+// because every function form tried changed the compiler's output (DESIGN.md 3.1
+// has the counts): the odd-tail owner test, the first-dot prologue and the
+// all-gather frame around res_exchange.
+// --------------------------------------------------------------------------
+// V(:,j+1) = w / ||w||, element-wise; a zero norm gives a zero column (as k_scale).
+// cb_round (gk_cb.hip) is the float counterpart -- the same rule, the quotient
+// then rounded once to FP32.
+__device__ __forceinline__ double2 res_unit(const double2 &v, double hn) {
+    return hn != 0.0 ? double2{v.x / hn, v.y / hn} : double2{0.0, 0.0};
+}
+// ... and the odd-length tail element, still in memory at *w: read only when the norm is
+// not zero (w by value or by reference reads it always: other code in every kernel)
+__device__ __forceinline__ double res_unit(const double *w, double hn) { return hn != 0.0 ? *w / hn : 0.0; }
+
+// The waves that do not run an all-gather, during it: pull `lines` 128-B lines from base
+// into L2, one dword load per line, lane l0 taking lines l0, l0 + step, ...  All loads land
+// in the one register `sink`, which the caller drains (s_waitcnt vmcnt(0) naming it) before
+// anything can reuse it.  PACE > 0: one load per lane per round, s_sleep PACE between
+// rounds, and the loop stops once *xdone is set (wave 0 holds the exchange's total); 0: all
+// at once.  (k_mgs_wres, k_mgs_wcb.  k_mgs_blk stops on a count of waves and keeps its own
+// loop: with the count as an argument the compare changes in both callers here.)
+template <int PACE>
+__device__ __forceinline__ void res_touch(const char *base, i64 lines, i64 l0, int step, const int *xdone, int &sink) {
+    for (i64 l = l0; l < lines; l += step) {
+        if constexpr (PACE > 0) {
+            if (*(const volatile int *)xdone) break;  // wave-uniform: one LDS word
+        }
+        const char *ptr = base + l * 128;
+        asm volatile("global_load_dword %0, %1, off" : "+v"(sink) : "v"(ptr) : "memory");
+        if constexpr (PACE > 0) __builtin_amdgcn_s_sleep(PACE);
+    }
+}
+
+// Workgroup 0 (every thread of it calls): H(1:j, j) from the LDS column hsh, then
+// ||w|| = H(j+1, j), to the device column and to the mapped host mirror -- hs before
+// hcopy, the norm last.  The barrier orders thread 0's last hsh update.
+template <int NT>
+__device__ __forceinline__ void res_store_hcol(const ResArgs &a, const double *hsh, int j, double hn) {
+    if (blockIdx.x != 0) return;
+    __syncthreads();
+    for (int k = threadIdx.x; k < j; k += NT) {
+        a.hs[k] = hsh[k];
+        a.hcopy[k] = hsh[k];
+    }
+    if (threadIdx.x == 0) {
+        a.hs[j] = hn;
+        a.hcopy[j] = hn;
+    }
 }
 
 // Wave 0 of every workgroup: sum the workgroup's wave partials sm[0..RWAVES)

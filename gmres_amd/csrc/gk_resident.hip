@@ -267,32 +267,22 @@ __global__ __launch_bounds__(RT, 2) void k_mgs_res(ResArgs a) {
 #pragma unroll
         for (int k = 0; k < R2; ++k)
             if (c0 + k < cend)
-                O2[(c0 + k) * DT + td] = hn != 0.0 ? double2{wr[k].x / hn, wr[k].y / hn} : double2{0.0, 0.0};
+                O2[(c0 + k) * DT + td] = res_unit(wr[k], hn);
         if constexpr (L2 > 0) {
             for (int k = 0; k < L2; ++k)
                 if (l0 + k < lend) {
                     const double2 v = lw[k * DT + td];
-                    O2[(l0 + k) * DT + td] = hn != 0.0 ? double2{v.x / hn, v.y / hn} : double2{0.0, 0.0};
+                    O2[(l0 + k) * DT + td] = res_unit(v, hn);
                 }
         }
         for (i64 e = sbase; e < n2; e += sstride) {
             const double2 v = W2[e];
-            O2[e] = hn != 0.0 ? double2{v.x / hn, v.y / hn} : double2{0.0, 0.0};
+            O2[e] = res_unit(v, hn);
         }
-        if ((a.n & 1) && blockIdx.x == gridDim.x - 1 && td == 0) a.vout[a.n - 1] = hn != 0.0 ? a.w[a.n - 1] / hn : 0.0;
+        if ((a.n & 1) && blockIdx.x == gridDim.x - 1 && td == 0) a.vout[a.n - 1] = res_unit(a.w + a.n - 1, hn);
     }
     clk.finish(a.stamps, mode);
-    if (blockIdx.x == 0) {  // H(1:j+1, j) to the device column and the mapped host mirror
-        __syncthreads();
-        for (int k = t; k < j; k += RT) {
-            a.hs[k] = hsh[k];
-            a.hcopy[k] = hsh[k];
-        }
-        if (t == 0) {
-            a.hs[j] = hn;
-            a.hcopy[j] = hn;
-        }
-    }
+    res_store_hcol<RT>(a, hsh, j, hn);
 }
 
 // --------------------------------------------------------------------------
@@ -733,14 +723,7 @@ __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
                 const i64 r0 = c0 + CARRY, r1 = cend;
                 const i64 lines = (i64)32 * (r1 - r0 < TCH ? (r1 - r0 > 0 ? r1 - r0 : 0) : TCH);
                 const char *base = reinterpret_cast<const char *>(V2 + (i64)touch_col * ld2 + r0 * WT);
-                for (i64 l = t - 64; l < lines; l += WT - 64) {
-                    if constexpr (PACE > 0) {
-                        if (*(volatile int *)&xdone) break;  // wave-uniform: one LDS word
-                    }
-                    const char *ptr = base + l * 128;
-                    asm volatile("global_load_dword %0, %1, off" : "+v"(touch_sink) : "v"(ptr) : "memory");
-                    if constexpr (PACE > 0) __builtin_amdgcn_s_sleep(PACE);
-                }
+                res_touch<PACE>(base, lines, t - 64, WT - 64, &xdone, touch_sink);
             }
         }
         __syncthreads();
@@ -890,29 +873,19 @@ __global__ __launch_bounds__(WT, 1) void k_mgs_wres(ResArgs a) {
 #pragma unroll
     for (int k = 0; k < RW; ++k)
         if (PIPE || c0 + k < cend)  // (the pipelined instantiation runs on full workgroups only)
-            O2[(c0 + k) * WT + t] = hn != 0.0 ? double2{wr[k].x / hn, wr[k].y / hn} : double2{0.0, 0.0};
+            O2[(c0 + k) * WT + t] = res_unit(wr[k], hn);
     for (int k = 0; k < LW; ++k)
         if (PIPE || l0 + k < lend) {
             const double2 v = lw[k * WT + t];
-            O2[(l0 + k) * WT + t] = hn != 0.0 ? double2{v.x / hn, v.y / hn} : double2{0.0, 0.0};
+            O2[(l0 + k) * WT + t] = res_unit(v, hn);
         }
     for (i64 e = sbase; e < n2; e += sstride) {
         const double2 v = W2[e];
-        O2[e] = hn != 0.0 ? double2{v.x / hn, v.y / hn} : double2{0.0, 0.0};
+        O2[e] = res_unit(v, hn);
     }
-    if ((a.n & 1) && blockIdx.x == gridDim.x - 1 && t == 0) a.vout[a.n - 1] = hn != 0.0 ? a.w[a.n - 1] / hn : 0.0;
+    if ((a.n & 1) && blockIdx.x == gridDim.x - 1 && t == 0) a.vout[a.n - 1] = res_unit(a.w + a.n - 1, hn);
     clk.finish(a.stamps, mode);
-    if (mode == RES_MGS && blockIdx.x == 0) {
-        __syncthreads();
-        for (int k = t; k < j; k += WT) {
-            a.hs[k] = hsh[k];
-            a.hcopy[k] = hsh[k];
-        }
-        if (t == 0) {
-            a.hs[j] = hn;
-            a.hcopy[j] = hn;
-        }
-    }
+    if (mode == RES_MGS) res_store_hcol<WT>(a, hsh, j, hn);
 }
 
 
@@ -1117,24 +1090,14 @@ __global__ __launch_bounds__(NT, 1) void k_mgs_wpc(ResArgs a) {
 #pragma unroll
     for (int k = 0; k < RW; ++k)
         if (c0 + k < cend)
-            O2[(c0 + k) * NT + t] = hn != 0.0 ? double2{wr[k].x / hn, wr[k].y / hn} : double2{0.0, 0.0};
+            O2[(c0 + k) * NT + t] = res_unit(wr[k], hn);
     for (i64 e = sbase; e < n2; e += sstride) {
         const double2 v = W2[e];
-        O2[e] = hn != 0.0 ? double2{v.x / hn, v.y / hn} : double2{0.0, 0.0};
+        O2[e] = res_unit(v, hn);
     }
-    if ((a.n & 1) && blockIdx.x == gridDim.x - 1 && t == 0) a.vout[a.n - 1] = hn != 0.0 ? a.w[a.n - 1] / hn : 0.0;
+    if ((a.n & 1) && blockIdx.x == gridDim.x - 1 && t == 0) a.vout[a.n - 1] = res_unit(a.w + a.n - 1, hn);
     clk.finish(a.stamps, mode);
-    if (blockIdx.x == 0) {
-        __syncthreads();
-        for (int k = t; k < j; k += NT) {
-            a.hs[k] = hsh[k];
-            a.hcopy[k] = hsh[k];
-        }
-        if (t == 0) {
-            a.hs[j] = hn;
-            a.hcopy[j] = hn;
-        }
-    }
+    res_store_hcol<NT>(a, hsh, j, hn);
 }
 
 
@@ -1245,6 +1208,14 @@ i64 wonly_bytes(i64 n2, int G) {
 
 static bool wonly_pays(i64 n2, int G) { return wonly_bytes(n2, G) < pairs_bytes(n2, G); }
 
+void res_spread(i64 n2, i64 dt, int G, int rmax, int lmax, int &r2e, int &l2e, i64 &nres2) {
+    const i64 nchf = n2 / dt;
+    r2e = (int)std::min<i64>(rmax, (nchf + G - 1) / G);
+    const i64 rest = std::max<i64>(0, nchf - (i64)G * r2e);
+    l2e = (int)std::min<i64>(lmax, (rest + G - 1) / G);
+    nres2 = std::min<i64>(nchf, (i64)G * (r2e + l2e)) * dt;
+}
+
 // The variant a slab of nloc local unknowns runs on (pure: no context, no
 // device; gk_res_plan_query exposes it so the CPU tests pin what every
 // production split selects).
@@ -1264,18 +1235,8 @@ void plan_resident(i64 nloc, int gmax, int cap, int tune_wonly, bool hh, bool nt
     static const int pfs[] = {2, 4, 8};
     for (int s : pfs)
         if (s <= cap && (p.r2 == 0 || p.r2 < need)) p.r2 = s;
-    // Spread the resident chunks evenly: every workgroup holds ceil(chunks / G)
-    // register chunks (at most the variant's R), then the same for LDS -- a
-    // contiguous fill would leave the last workgroups idle and make the first
-    // ones set the pace of every all-gather (2048^2: slowest pass 10.2 us vs
-    // 4.3 us median).
-    auto spread = [&](i64 dt, int rmax, int lmax) {
-        const i64 nchf = n2 / dt, G = p.G;
-        p.r2e = (int)std::min<i64>(rmax, (nchf + G - 1) / G);
-        const i64 rest = std::max<i64>(0, nchf - G * p.r2e);
-        p.l2e = (int)std::min<i64>(lmax, (rest + G - 1) / G);
-        p.nres2 = std::min<i64>(nchf, G * (p.r2e + p.l2e)) * dt;
-    };
+    // the resident chunks spread evenly over the p.G workgroups chosen below
+    auto spread = [&](i64 dt, int rmax, int lmax) { res_spread(n2, dt, p.G, rmax, lmax, p.r2e, p.l2e, p.nres2); };
     // The column-cache variant where it moves fewer bytes than both large-slab
     // variants: it streams as fast as k_mgs_res (2896^2: 10.25 vs 14 B/unknown -> 15.5
     // vs 18.8 us per projection; 2048^2: 8 vs 10 -> 8.8 vs 9.6,
@@ -1383,8 +1344,6 @@ void plan_info(const ResPlan &p, bool on, long long *info) {
 }
 
 // -------------------------------------------------------------- launchers ---
-namespace {
-
 int fail(std::string &msg, int code, const char *fmt, ...) {
     char buf[512];
     va_list ap;
@@ -1395,7 +1354,6 @@ int fail(std::string &msg, int code, const char *fmt, ...) {
     return code;
 }
 
-// the dynamic-LDS size of `kernel` allowed on this device (memo: per instantiation)
 int dyn_lds(const void *kernel, int dev, int lds, std::atomic<int> *memo, std::string &msg) {
     if (dev < 0 || dev >= ATTR_DEVS) return fail(msg, GK_ERR_ARG, "device id %d out of range", dev);
     const hipError_t e = ensure_dyn_lds(kernel, dev, lds, memo);
@@ -1405,11 +1363,13 @@ int dyn_lds(const void *kernel, int dev, int lds, std::atomic<int> *memo, std::s
     return GK_OK;
 }
 
-int launched(std::string &msg) {
+int launched(const char *what, std::string &msg) {
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(msg, GK_ERR_HIP, "resident step launch: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(msg, GK_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
     return GK_OK;
 }
+
+namespace {
 
 template <int R2, int L2, bool PF, bool NT, bool CW, int MODE>
 int launch_res_m(const ResPlan &p, const ResArgs &a, int dev, hipStream_t st, std::string &msg) {
@@ -1417,7 +1377,7 @@ int launch_res_m(const ResPlan &p, const ResArgs &a, int dev, hipStream_t st, st
     const int e = dyn_lds(reinterpret_cast<const void *>(&k_mgs_res<R2, L2, PF, NT, CW, MODE>), dev, p.lds, attr, msg);
     if (e != GK_OK) return e;
     k_mgs_res<R2, L2, PF, NT, CW, MODE><<<p.G, RT, p.lds, st>>>(a);
-    return launched(msg);
+    return launched("resident step", msg);
 }
 
 template <int R2, int L2, bool PF, bool NT, bool CW>
@@ -1439,7 +1399,7 @@ int launch_wres_m(const ResPlan &p, const ResArgs &a, int dev, hipStream_t st, s
         dyn_lds(reinterpret_cast<const void *>(&k_mgs_wres<RW, LW, MODE, WBT, PIPE, CARRY>), dev, p.lds, attr, msg);
     if (e != GK_OK) return e;
     k_mgs_wres<RW, LW, MODE, WBT, PIPE, CARRY><<<p.G, WT, p.lds, st>>>(a);
-    return launched(msg);
+    return launched("resident step", msg);
 }
 
 int launch_wres(const ResPlan &p, const ResArgs &a, int dev, hipStream_t st, std::string &msg) {
@@ -1480,7 +1440,7 @@ int launch_wpc_k(const ResPlan &p, const ResArgs &a, int dev, hipStream_t st, st
                           p.lds, attr, msg);
     if (e != GK_OK) return e;
     k_mgs_wpc<RW, RX, LX, MODE, WBT, RES_PC_NT><<<p.G, RES_PC_NT, p.lds, st>>>(a);
-    return launched(msg);
+    return launched("resident step", msg);
 }
 
 template <int MODE>
@@ -1496,11 +1456,7 @@ int launch_wpc_m(const ResPlan &p, const ResArgs &a, int dev, hipStream_t st, st
 int res_launch(const ResPlan &p, const ResArgs &a, int dev, hipStream_t st, std::string &msg) {
     if (p.bvar >= 0) {
         if (a.mode != RES_MGS) return fail(msg, GK_ERR_STATE, "the blocked step is the MGS-R step's only");
-        const int e = blk_launch(p.bvar, p.blk, a, p.G, p.lds, dev, st);
-        if (e != 0)
-            return fail(msg, GK_ERR_HIP, "k_mgs_blk (S=%d, variant %d): %s", p.blk, p.bvar,
-                        hipGetErrorString(static_cast<hipError_t>(e)));
-        return GK_OK;
+        return blk_launch(p.bvar, p.blk, a, p.G, p.lds, dev, st, msg);
     }
     if (p.wo) return launch_wres(p, a, dev, st, msg);
     if (p.pc) {

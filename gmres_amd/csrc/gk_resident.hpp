@@ -40,6 +40,13 @@ GK_HIDDEN void plan_resident(i64 nloc, int gmax, int cap, int tune_wonly, bool h
                              int tune_carry = -1);
 GK_HIDDEN bool nt_auto_for(i64 max_nloc);
 
+// The even spread of a slab's whole chunks (n2 double2 in chunks of dt, one per thread)
+// over G workgroups: every workgroup holds ceil(chunks / G) register chunks (at most
+// rmax), then the same for LDS (at most lmax); nres2 = the double2 held on chip.  A
+// contiguous fill would leave the last workgroups idle and make the first ones set the
+// pace of every all-gather (2048^2: slowest pass 10.2 us vs 4.3 us median).
+GK_HIDDEN void res_spread(i64 n2, i64 dt, int G, int rmax, int lmax, int &r2e, int &l2e, i64 &nres2);
+
 // gk_res_plan_query / gk_res_info layout
 enum { RPI_VARIANT = 0, RPI_G, RPI_R2, RPI_L2, RPI_PF, RPI_CW, RPI_WO, RPI_NT, RPI_R2E, RPI_L2E, RPI_LDS, RPI_NRES2, RPI_PIPE,
        RPI_CHEB_STEN, RPI_WT, RPI_BLK, RPI_CARRY };
@@ -48,5 +55,13 @@ GK_HIDDEN void plan_info(const ResPlan &p, bool on, long long *info);
 // Launch plan p's kernel for a.mode on stream st of device dev.  Returns GK_OK, or a
 // GK_ERR_* code with its text in msg (the caller's set_err).
 GK_HIDDEN int res_launch(const ResPlan &p, const ResArgs &a, int dev, hipStream_t st, std::string &msg);
+
+// What the launchers of the resident kernels (gk_resident.hip, gk_blk.hip, gk_cb.hip) share.
+// msg = the formatted text; returns code.
+GK_HIDDEN int fail(std::string &msg, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+// Allow `kernel` lds bytes of dynamic LDS on device dev (memo[ATTR_DEVS]: one per instantiation).
+GK_HIDDEN int dyn_lds(const void *kernel, int dev, int lds, std::atomic<int> *memo, std::string &msg);
+// GK_OK, or the launch error of the `what` just launched.
+GK_HIDDEN int launched(const char *what, std::string &msg);
 
 }  // namespace gk
