@@ -46,6 +46,7 @@ GK_TUNE_RIGHT_FUSED = 31
 GK_TUNE_RES_PIPE_CARRY = 32
 GK_SIDE_LEFT, GK_SIDE_RIGHT = 0, 1
 GK_BASIS_F64, GK_BASIS_F32 = 0, 1
+GK_HH_PREC_NONE, GK_HH_PREC_LEFT, GK_HH_PREC_RIGHT = 0, 1, 2
 GK_ERR_ARG, GK_ERR_STATE = -1, -4
 GK_PREC_IDENTITY, GK_PREC_CBPR2, GK_PREC_CHEB = 0, 1, 2
 (GK_KID_PROJ, GK_KID_STENCIL, GK_KID_SCALE, GK_KID_UPDATE, GK_KID_COMM, GK_KID_OTHER, GK_KID_RES, GK_KID_PREC,

@@ -94,7 +94,8 @@ def _scratch_kernels(remarks: str, name: str) -> list[str]:
 def _compile_link(so: str, defines: list[str]) -> None:
     """Compile the HIP translation units in parallel into objects beside `so`,
     then link them into the shared library.  The Chebyshev pass, the resident
-    step kernels and the two-level right-preconditioning march must not spill
+    step kernels, the two-level right-preconditioning march and the stencil marches
+    (among them the accumulating cbpr2 sweep of the right-preconditioned update) must not spill
     registers to scratch (gk_cheb.hip refuses such a
     pass at run time; a spilled resident kernel holds w in scratch memory): the
     build fails here, naming them."""
@@ -111,7 +112,7 @@ def _compile_link(so: str, defines: list[str]) -> None:
         err = p.communicate()[1]
         sys.stderr.write("".join(l + "\n" for l in err.splitlines() if "warning:" in l or "error" in l))
         for name in ("k_cheb_fused", "k_mgs_wpc", "k_mgs_wres", "k_mgs_res", "k_mgs_blk", "k_right_cbpr2",
-                     "k_mgs_wcb"):
+                     "k_mgs_wcb", "k_stencil"):
             bad += _scratch_kernels(err, name)
     if any(p.returncode for p in procs):
         raise subprocess.CalledProcessError(max(p.returncode for p in procs), "hipcc")

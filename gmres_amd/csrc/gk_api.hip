@@ -160,6 +160,9 @@ int stencil(gk_ctx *c, int op, int acc, gk::StArgs a) {
         case gk::OP_RESID: return launch_stencil_a<gk::OP_RESID>(c, acc, a);
         case gk::OP_CBPR2: return launch_stencil_a<gk::OP_CBPR2>(c, acc, a);
         case gk::OP_CHEB_FIRST: return launch_stencil_a<gk::OP_CHEB_FIRST>(c, acc, a);
+        case gk::OP_CBPR2_ADD:  // the update's accumulate form carries no reduction
+            if (acc != gk::ACC_NONE) return set_err(GK_ERR_ARG, "OP_CBPR2_ADD: reduction %d", acc);
+            return launch_stencil_o<gk::OP_CBPR2_ADD, gk::ACC_NONE>(c, a);
         default: return launch_stencil_a<gk::OP_CHEB_ITER>(c, acc, a);
     }
 }
@@ -739,6 +742,27 @@ int op_right(gk_ctx *c, const double *v, double *out, int acc, const double *vdo
     a.vdot = vdot;
     a.part = part;
     return stencil(c, gk::OP_PLAIN, acc, a);
+}
+
+// x += M^-1 t, the cycle-end update of a right-preconditioned Householder cycle (M not
+// the identity; t is not z).  Where k_right_cbpr2 applies, ONE march: the cbpr2 sweep
+// with the accumulating output (OP_CBPR2_ADD: t and x read, x written, z never stored).
+// Else z = M^-1 t by the preconditioner's own route and k_add -- the same expressions
+// in the same order, so x is bit-identical on both routes.
+int add_precond(gk_ctx *c, const double *t) {
+    if (right_fused_ok(c)) {
+        gk::StArgs a{};
+        a.x = t;
+        a.in1 = c->x;
+        a.y = c->x;
+        cbpr2_coefs(c, &a.s1, &a.s2);
+        return stencil(c, gk::OP_CBPR2_ADD, gk::ACC_NONE, a);
+    }
+    CHK(precond_sweeps(c, t, c->z, gk::ACC_NONE, nullptr, nullptr));
+    ProfScope ps(c, GK_KID_UPDATE);
+    gk::k_add<<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->x, c->z, c->nloc);
+    LAUNCHCHK();
+    return GK_OK;
 }
 
 int owner_of(gk_ctx *c, i64 gidx) {
@@ -1454,6 +1478,17 @@ int gk_mgs_verr(gk_ctx *c, int n_out, int zero_last, double *v_err) {
 // the whole vector, so one rank only (N ranks keep the tree).
 static bool hh_seq_norms(const gk_ctx *c) { return c->tune_hh_norm_order != 0 && c->nranks == 1; }
 
+// The `precondition` argument of a cycle start or a step: one of GK_HH_PREC_*, and the left
+// side only where the context's MGS-R side is left too (GK_HH_PREC_RIGHT asks for its side itself).
+static int hh_prec_arg(const gk_ctx *c, int precondition) {
+    if (precondition != GK_HH_PREC_NONE && precondition != GK_HH_PREC_LEFT && precondition != GK_HH_PREC_RIGHT)
+        return set_err(GK_ERR_ARG, "precondition = %d is none of GK_HH_PREC_NONE / _LEFT / _RIGHT", precondition);
+    if (precondition == GK_HH_PREC_LEFT && right_prec(c))
+        return set_err(GK_ERR_STATE, "precondition = GK_HH_PREC_LEFT preconditions on the left only: "
+                                     "gk_set_precond_side(ctx, GK_SIDE_LEFT) first, or GK_HH_PREC_RIGHT");
+    return GK_OK;
+}
+
 static int hh_pivot(gk_ctx *c, int j, double *hostout, int nout) {
     // hb[0..j] = w(1:j+1) from the owning rank, broadcast
     const int root = owner_of(c, j);
@@ -1472,12 +1507,10 @@ int gk_hh_cycle_start(gk_ctx *c, int precondition, double *g1) {
     HIPCHK(hipSetDevice(c->dev));
     if (c->nranks > 1 && c->rank == 0 && c->nloc < c->m + 2)
         return set_err(GK_ERR_ARG, "Householder path needs the first slab to hold m+2 unknowns");
-    if (precondition && right_prec(c))
-        return set_err(GK_ERR_STATE, "Householder GMRES preconditions on the left only: "
-                                     "gk_set_precond_side(ctx, GK_SIDE_LEFT) first");
-    if (precondition) {
+    CHK(hh_prec_arg(c, precondition));
+    if (precondition == GK_HH_PREC_LEFT) {
         CHK(op_precond(c, c->x, c->w, true, gk::ACC_NORM, nullptr, slot(c, 0)));
-    } else {
+    } else {  // none, or right: the Arnoldi residual is the true residual b - A x
         CHK(halo(c, c->x));
         gk::StArgs a{};
         a.x = c->x;
@@ -1511,6 +1544,7 @@ int gk_hh_cycle_start(gk_ctx *c, int precondition, double *g1) {
     CHK(d2h_sync(c, g1, c->hcol, 1));
     c->cycle_hh = true;
     c->cycle_mgs = false;
+    c->hh_prec = precondition;
     return GK_OK;
 }
 
@@ -1519,9 +1553,10 @@ int gk_hh_step_async(gk_ctx *c, int j, int precondition) {
     if (cb_on(c)) return set_err(GK_ERR_STATE, "the FP32 basis is MGS-R only (gk_set_basis_precision)");
     if (j < 1 || j > c->m) return set_err(GK_ERR_ARG, "step j=%d outside 1..%d", j, c->m);
     if (!c->cycle_hh) return set_err(GK_ERR_STATE, "gk_hh_step before gk_hh_cycle_start");
-    if (precondition && right_prec(c))
-        return set_err(GK_ERR_STATE, "Householder GMRES preconditions on the left only: "
-                                     "gk_set_precond_side(ctx, GK_SIDE_LEFT) first");
+    CHK(hh_prec_arg(c, precondition));
+    if ((precondition == GK_HH_PREC_RIGHT) != (c->hh_prec == GK_HH_PREC_RIGHT))
+        return set_err(GK_ERR_STATE, "gk_hh_step with precondition = %d in a cycle started with %d", precondition,
+                       c->hh_prec);
     HIPCHK(hipSetDevice(c->dev));
     const i64 ld = c->ld;
     double *P = c->V;
@@ -1539,10 +1574,12 @@ int gk_hh_step_async(gk_ctx *c, int j, int precondition) {
         LAUNCHCHK();
     }
     CHK(reflect_chain_down(c, c->vj, j, j - 1, fuse ? RESF_UNIT_INIT : 0));
-    // w = M^-1 A v_j (or A v_j), fused with <w, P_1>
+    // w = M^-1 A v_j (right: A M^-1 v_j; none, or the identity on the right: A v_j), fused with <w, P_1>
     int s0 = 0, s1 = 1;
-    if (precondition) {
+    if (precondition == GK_HH_PREC_LEFT) {
         CHK(op_precond(c, c->vj, c->w, false, gk::ACC_DOT, P, slot(c, s0)));
+    } else if (precondition == GK_HH_PREC_RIGHT && c->pkind != GK_PREC_IDENTITY) {
+        CHK(op_right(c, c->vj, c->w, gk::ACC_DOT, P, slot(c, s0)));
     } else {
         CHK(halo(c, c->vj));
         gk::StArgs a{};
@@ -1639,7 +1676,9 @@ int gk_hh_update_x(gk_ctx *c, const double *y, int n_out) {
         LAUNCHCHK();
     }
     CHK(reflect_chain_down(c, c->w, n_out));
-    {
+    if (c->hh_prec == GK_HH_PREC_RIGHT && c->pkind != GK_PREC_IDENTITY) {  // x += M^-1 t, t in w
+        CHK(add_precond(c, c->w));
+    } else {
         ProfScope ps(c, GK_KID_UPDATE);
         gk::k_add<<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->x, c->w, c->nloc);
         LAUNCHCHK();

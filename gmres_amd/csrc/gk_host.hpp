@@ -143,6 +143,7 @@ struct gk_ctx {
     bool prof_on_step = true;
     // state
     bool cycle_mgs = false, cycle_hh = false;
+    int hh_prec = 0;          // GK_HH_PREC_* the Householder cycle opened last was started with
     double beta0 = -1.0;
     // profiling
     bool prof = false;
@@ -204,7 +205,8 @@ int fill_hash(gk_ctx *c, double *x, unsigned long long seed);  // k_fill_hash of
 // running gk_sr_* solve -- later gk_sr_iterate / status / history refuse until the
 // next gk_sr_start.
 inline void sr_invalidate(gk_ctx *c) { c->sr_solver = -1; }
-// Householder GMRES and the short-recurrence solvers precondition on the left only.
+// The context's side: the MGS-R cycle's.  The short-recurrence solvers and Householder's
+// GK_HH_PREC_LEFT precondition on the left only; GK_HH_PREC_RIGHT does not ask the context.
 inline bool right_prec(const gk_ctx *c) { return c->side == GK_SIDE_RIGHT && c->pkind != GK_PREC_IDENTITY; }
 
 // Compressed basis (gk_cb.hpp): the FP32 columns in the lower half of V, the two widened

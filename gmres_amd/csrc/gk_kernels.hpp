@@ -404,13 +404,17 @@ enum {
     OP_CBPR2 = 2,      // x = z: zp = z/d, y = zp + alpha*(z - A zp) (chebyshev.f90:27-37)
     OP_CHEB_FIRST = 3, // x = r: d0 = r/theta; first Chebyshev iteration
     OP_CHEB_ITER = 4,  // x = d: next Chebyshev iteration
+    OP_CBPR2_ADD = 5,  // x = t: OP_CBPR2's z, y = in1 + z -- the right-preconditioned update
+                       // x += M^-1 t with y = in1 = the solution (read and written at the
+                       // lane's own points only); z is never stored: t and x read, x written,
+                       // 24 B/unknown where OP_CBPR2 + k_add move 40
 };
 
 struct StArgs {
     const double *x;    // operand, nlines*N
     const double *hlo;  // line -1 (nullptr: physical boundary)
     const double *hhi;  // line nlines (nullptr: physical boundary)
-    const double *in1;  // RESID: b ; CHEB_ITER: residual r_k
+    const double *in1;  // RESID: b ; CHEB_ITER: residual r_k ; CBPR2_ADD: the vector z is added to
     const double *in2;  // CHEB_ITER: running sum z_k
     double *y;          // main output
     double *o_res;      // CHEB: r_{k+1} (nullptr on the last iteration)
@@ -431,7 +435,7 @@ __global__ __launch_bounds__(TPB) void k_stencil(StArgs a) {
     const int j0 = blockIdx.y * a.JT;
     const int j1 = min(j0 + a.JT, a.nlines);
     // operand transform at load (CBPR2: /d ; CHEB_FIRST: /theta)
-    constexpr bool XF = (OP == OP_CBPR2 || OP == OP_CHEB_FIRST);
+    constexpr bool XF = (OP == OP_CBPR2 || OP == OP_CBPR2_ADD || OP == OP_CHEB_FIRST);
     const double dv = a.s1;
     double acc = 0.0;
 
@@ -469,7 +473,7 @@ __global__ __launch_bounds__(TPB) void k_stencil(StArgs a) {
             if (i0 + VEC >= N) right = 0.0;
             double yv[VEC];
             double in1v[VEC], in2v[VEC];
-            if (OP == OP_RESID || OP == OP_CHEB_ITER) ld_vec<VEC>(a.in1 + row + i0, act, in1v);
+            if (OP == OP_RESID || OP == OP_CHEB_ITER || OP == OP_CBPR2_ADD) ld_vec<VEC>(a.in1 + row + i0, act, in1v);
             if (OP == OP_CHEB_ITER) ld_vec<VEC>(a.in2 + row + i0, act, in2v);
             // the dot operand is issued with the line loads, not after the store
             double vd[VEC];
@@ -487,6 +491,9 @@ __global__ __launch_bounds__(TPB) void k_stencil(StArgs a) {
                     yv[k] = in1v[k] - ax;
                 } else if (OP == OP_CBPR2) {
                     yv[k] = tc[k] + a.s2 * (rc[k] - ax);
+                } else if (OP == OP_CBPR2_ADD) {  // k_add's x + z on OP_CBPR2's z
+                    const double z = tc[k] + a.s2 * (rc[k] - ax);
+                    yv[k] = in1v[k] + z;
                 } else if (OP == OP_CHEB_FIRST) {
                     // res = r - A d0 ; d1 = c1*d0 + c2*res ; z = d0 + d1
                     const double res = rc[k] - ax;

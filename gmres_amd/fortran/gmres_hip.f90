@@ -26,6 +26,7 @@ module gmres_hip_c
     integer(c_int), parameter :: GK_PREC_IDENTITY = 0, GK_PREC_CBPR2 = 1, GK_PREC_CHEB = 2
     integer(c_int), parameter :: GK_SIDE_LEFT = 0, GK_SIDE_RIGHT = 1
     integer(c_int), parameter :: GK_BASIS_F64 = 0, GK_BASIS_F32 = 1
+    integer(c_int), parameter :: GK_HH_PREC_NONE = 0, GK_HH_PREC_LEFT = 1, GK_HH_PREC_RIGHT = 2
     integer(c_int), parameter :: GK_VEC_X = 0, GK_VEC_B = 1
     integer(c_int), parameter :: GK_SR_PCG = 0, GK_SR_BICGSTAB = 1
     integer(c_int), parameter :: GK_LC_COPY = 0, GK_LC_AXPY = 1, GK_LC_AXPY2 = 2, GK_LC_XPAYMZ = 3, GK_LC_ZERO = 4
@@ -309,6 +310,7 @@ module gmres_hip
 
     public :: stencil_vector, precond
     public :: GK_SIDE_LEFT, GK_SIDE_RIGHT, GK_BASIS_F64, GK_BASIS_F32
+    public :: GK_HH_PREC_NONE, GK_HH_PREC_LEFT, GK_HH_PREC_RIGHT
     public :: hip_poisson5, hip_identity, hip_cbpr2, hip_chebyshev
     public :: gmres_mgsr_hip, gmres_hh_hip, gmres_hh_prec_hip, hip_release
     public :: pcg_hip, pbicgstab_hip, pcg_drive, bicgstab_drive, pcg_drive_seq, bicgstab_drive_seq
@@ -472,12 +474,16 @@ contains
     !> Householder GMRES(m) on a device context.  midcycle_exit = .false.:
     !> gmres_hh_omp (gmres_hh.f90:211-385, always full cycles, no preconditioner
     !> at cycle start when precondition = 0); .true.: gmres_hh_prec_omp
-    !> (:388-566, `converged` latch).
+    !> (:388-566, `converged` latch).  precondition is a GK_HH_PREC_* value; optional
+    !> side = GK_SIDE_RIGHT turns a preconditioned solve into GK_HH_PREC_RIGHT
+    !> (w = A M^-1 v_j, x += M^-1 (P_1..P_n [y;0])): final_err(j) is then the true
+    !> relative residual.  The loop is the same on either side.
     integer function hh_drive(ctx, m, tol, beta0, precondition, midcycle_exit, max_cyc, x, final_err, &
                               v_err, n_out, stages_out, want_verr, want_hist, hist_res, hist_ferr, &
-                              n_cycles, keep_x) result(st)
+                              n_cycles, keep_x, side) result(st)
         type(c_ptr), intent(in) :: ctx
         integer, intent(in) :: m, max_cyc, precondition
+        integer, intent(in), optional :: side
         logical, intent(in) :: midcycle_exit
         real(8), intent(in) :: tol, beta0
         real(8), intent(out) :: x(*), final_err(m), v_err(m + 1)
@@ -488,7 +494,12 @@ contains
         real(8), allocatable :: H(:, :), g(:), y(:), cs(:), sn(:), hcol(:)
         real(8) :: g1
         integer :: k, j
+        integer(c_int) :: pc
         logical :: converged
+        pc = int(precondition, c_int)
+        if (present(side)) then
+            if (side == GK_SIDE_RIGHT .and. pc /= GK_HH_PREC_NONE) pc = GK_HH_PREC_RIGHT
+        end if
         allocate (H(m + 1, m), g(m + 1), y(m), cs(m), sn(m), hcol(m + 1))
         final_err = 0.0d0; v_err = 0.0d0; cs = 0.0d0; sn = 0.0d0
         n_out = 0; stages_out = 0; n_cycles = 0
@@ -496,16 +507,16 @@ contains
         st = gk_zero_x(ctx); if (st /= GK_OK) return
         do k = 1, max_cyc
             g = 0.0d0; H = 0.0d0
-            st = gk_hh_cycle_start(ctx, precondition, g1); if (st /= GK_OK) return
+            st = gk_hh_cycle_start(ctx, pc, g1); if (st /= GK_OK) return
             g(1) = g1
             if (.not. converged) then
-                st = gk_hh_step_async(ctx, 1, precondition); if (st /= GK_OK) return
+                st = gk_hh_step_async(ctx, 1, pc); if (st /= GK_OK) return
             end if
             do j = 1, m
                 if (converged) exit
                 n_out = j
                 if (j < m) then  ! pipelined as in mgsr_drive
-                    st = gk_hh_step_async(ctx, j + 1, precondition); if (st /= GK_OK) return
+                    st = gk_hh_step_async(ctx, j + 1, pc); if (st /= GK_OK) return
                 end if
                 st = gk_hh_step_wait(ctx, j, hcol); if (st /= GK_OK) return
                 H(1:j + 1, j) = hcol(1:j + 1)
@@ -931,8 +942,11 @@ contains
         call gk_require(gk_destroy(ctx), 'gk_destroy')
     end subroutine gmres_hh_hip
 
-    !> Drop-in for gmres_hh_prec_omp (src/gmres_hh.f90:388-398).
-    subroutine gmres_hh_prec_hip(Ax_vec, b, x, m, tol, final_err, v_err, n_out, stages_out, m_inv, params)
+    !> Drop-in for gmres_hh_prec_omp (src/gmres_hh.f90:388-398).  Optional
+    !> side = GK_SIDE_RIGHT (default left, the reference) preconditions on the right
+    !> (GK_HH_PREC_RIGHT): final_err(j) is then the true relative residual, as with
+    !> gmres_mgsr_hip(..., side=GK_SIDE_RIGHT).
+    subroutine gmres_hh_prec_hip(Ax_vec, b, x, m, tol, final_err, v_err, n_out, stages_out, m_inv, params, side)
         procedure(stencil_vector) :: Ax_vec
         real(8), intent(in) :: b(:)
         real(8), allocatable, intent(out) :: x(:)
@@ -942,16 +956,20 @@ contains
         integer, intent(out) :: n_out, stages_out
         procedure(precond) :: m_inv
         real(8), intent(in) :: params(:)
+        integer, intent(in), optional :: side
         type(c_ptr) :: ctx
         integer(c_int) :: kind, degree
-        integer :: ncyc
+        integer :: ncyc, sd
         real(8) :: dummy_h(1), dummy_f(1, 1)
         call require_device_op(Ax_vec, 'gmres_hh_prec_hip')
         call prec_kind(m_inv, params, kind, degree)
+        sd = GK_SIDE_LEFT
+        if (present(side)) sd = side
         allocate (x(size(b)), final_err(m), v_err(m + 1))
         ctx = solver_ctx(b, m, kind, degree, params)
-        call gk_require(hh_drive(ctx, m, tol, norm2(b), 1, .true., hip_max_restarts, x, final_err, v_err, &
-                                 n_out, stages_out, .true., .false., dummy_h, dummy_f, ncyc), 'gmres_hh_prec_hip')
+        call gk_require(hh_drive(ctx, m, tol, norm2(b), GK_HH_PREC_LEFT, .true., hip_max_restarts, x, final_err, &
+                                 v_err, n_out, stages_out, .true., .false., dummy_h, dummy_f, ncyc, side=sd), &
+                        'gmres_hh_prec_hip')
         call gk_require(gk_destroy(ctx), 'gk_destroy')
     end subroutine gmres_hh_prec_hip
 

@@ -7,23 +7,26 @@
 !! An optional third argument `right` runs the MGS-R solve alone, preconditioned
 !! on the right (side = GK_SIDE_RIGHT: its "Final residual" is the true one); `f32`
 !! runs it alone on the compressed basis (basis = GK_BASIS_F32: the Krylov columns
-!! stored as FP32).
+!! stored as FP32); `hhright` runs the Householder solve alone, preconditioned on the
+!! right (gmres_hh_prec_hip(..., side = GK_SIDE_RIGHT)), and prints its final residual
+!! a second time with every digit.
 program test_mfp_hip
     use gmres_hip
     implicit none
     integer :: nsize, max_iter, n_args
     character(len=32) :: arg_str
-    logical :: right, f32
+    logical :: right, f32, hhright
     n_args = command_argument_count()
     if (n_args < 2) then
-        print *, "usage ./test_mfp_hip <grid size> <iterations per restart> [right|f32]"
+        print *, "usage ./test_mfp_hip <grid size> <iterations per restart> [right|f32|hhright]"
         stop
     end if
-    right = .false.; f32 = .false.
+    right = .false.; f32 = .false.; hhright = .false.
     if (n_args >= 3) then
         call get_command_argument(3, arg_str)
         right = trim(arg_str) == 'right'
         f32 = trim(arg_str) == 'f32'
+        hhright = trim(arg_str) == 'hhright'
     end if
     call get_command_argument(1, arg_str)
     read (arg_str, *) nsize
@@ -34,8 +37,10 @@ program test_mfp_hip
         call run(nsize, max_iter, .true.)
         write (*, '(60("-"))')
     end if
-    call run(nsize, max_iter, .false.)
-    write (*, '(60("-"))')
+    if (.not. hhright) then
+        call run(nsize, max_iter, .false.)
+        write (*, '(60("-"))')
+    end if
     call hip_release()
 contains
     subroutine run(nsize, max_iter, householder)
@@ -49,7 +54,9 @@ contains
         params(1) = 8.2d0; params(2) = 0.2d0
         x = 1.0d0
         call hip_poisson5(x, b, nsize)   ! b = A*1: every solution entry must be 1.0
-        if (householder) then
+        if (householder .and. hhright) then
+            write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (Householder Chebyshev on the right, MI355X)'
+        else if (householder) then
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (Householder Chebyshev, MI355X)'
         else if (right) then
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR Chebyshev on the right, MI355X)'
@@ -60,7 +67,10 @@ contains
         end if
         write (*, '(A,I8,A18,I5,A8,ES10.2)') "N VARS=", nsize*nsize, " MAX ITERS/STAGE=", max_iter, " TOL=", tol
         call system_clock(c0, crate)
-        if (householder) then
+        if (householder .and. hhright) then
+            call gmres_hh_prec_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params, &
+                                   side=GK_SIDE_RIGHT)
+        else if (householder) then
             call gmres_hh_prec_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params)
         else if (right) then
             call gmres_mgsr_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params, &
@@ -76,6 +86,7 @@ contains
             ' Stages=', n_stages
         write (*, '(A30, ES12.4)') "Final ||I - V.t * V||:", verr(n_iter)
         write (*, '(A30, ES12.4)') 'Final residual:', errn(n_iter)
+        if (hhright) write (*, '(A30, ES24.16)') 'Final residual, every digit:', errn(n_iter)
         write (*, '(A30, ES12.4)') 'Max error L_max:', maxval(abs(x - 1.0d0))
         write (*, '(A30, ES12.4)') 'L2 norm:', norm2(x - 1.0d0)
         write (*, '(A30, 10F10.4)') 'First 10 solution elements', x(1:10)

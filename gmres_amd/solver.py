@@ -21,6 +21,7 @@ PREC = {"identity": nat.GK_PREC_IDENTITY, "none": nat.GK_PREC_IDENTITY,
         "cbpr2": nat.GK_PREC_CBPR2, "cheb": nat.GK_PREC_CHEB, "chebyshev": nat.GK_PREC_CHEB}
 SIDE = {"left": nat.GK_SIDE_LEFT, "right": nat.GK_SIDE_RIGHT}
 BASIS = {"f64": nat.GK_BASIS_F64, "f32": nat.GK_BASIS_F32}
+HH_PREC = {"none": nat.GK_HH_PREC_NONE, "left": nat.GK_HH_PREC_LEFT, "right": nat.GK_HH_PREC_RIGHT}
 MGSR_MF, MGSR_OMP = 0, 1
 
 
@@ -190,7 +191,8 @@ class Context:
                     side: str = "left") -> None:
         """side "left" (the reference's MGS-R) or "right": w = A M^-1 v_j and
         x += M^-1 (V y), so final_err is the true relative residual
-        (gk_set_precond_side; MGS-R only)."""
+        (gk_set_precond_side; the MGS-R cycle's side -- gmres_hh takes its own,
+        precondition="right")."""
         k = PREC[kind] if isinstance(kind, str) else int(kind)
         if side not in SIDE:
             raise ValueError(f"side must be 'left' or 'right', not {side!r}")
@@ -427,14 +429,28 @@ def gmres_mgsr(ctx: Context, tol: float = 1e-15, variant: int = MGSR_OMP, max_cy
     return r
 
 
-def gmres_hh(ctx: Context, tol: float = 1e-15, precondition: bool = False, midcycle_exit: bool | None = None,
+def hh_prec_mode(precondition) -> int:
+    """The GK_HH_PREC_* value of gmres_hh's `precondition`: False -> NONE, True -> LEFT,
+    "right" -> RIGHT ("left" and "none" are accepted too)."""
+    if isinstance(precondition, str):
+        try:
+            return HH_PREC[precondition]
+        except KeyError:
+            raise ValueError(f"precondition must be a bool, 'none', 'left' or 'right', not {precondition!r}") from None
+    return nat.GK_HH_PREC_LEFT if precondition else nat.GK_HH_PREC_NONE
+
+
+def gmres_hh(ctx: Context, tol: float = 1e-15, precondition: bool | str = False, midcycle_exit: bool | None = None,
              max_cycles: int = 1000, want_verr: bool = True, want_hist: bool = False,
              want_x: bool = True) -> SolveResult:
     """Householder GMRES(m): precondition=False -> gmres_hh_omp (full cycles);
-    precondition=True -> gmres_hh_prec_omp (in-cycle convergence latch).
+    precondition=True -> gmres_hh_prec_omp (in-cycle convergence latch);
+    precondition="right" -> the same loop preconditioned on the right (GK_HH_PREC_RIGHT,
+    whatever the context's side is): final_err is the true relative residual.
     want_x = False: the solution stays in HBM (result x empty; ctx.get_x() later)."""
+    precondition = hh_prec_mode(precondition)
     if midcycle_exit is None:
-        midcycle_exit = precondition
+        midcycle_exit = precondition != nat.GK_HH_PREC_NONE
     m = ctx.m
     x = np.zeros(ctx.nloc if want_x else 1)
     fe = np.zeros(m)

@@ -173,10 +173,12 @@ int gk_set_precond(gk_ctx *ctx, int kind, const double *params, int nparams, int
  *                  rank (GK_TUNE_RIGHT_FUSED), else as the preconditioner's own
  *                  launches followed by the stencil.
  * Setting the side ends a running gk_sr_* solve and an open GMRES cycle (steps
- * return GK_ERR_STATE until the next cycle start).  Householder GMRES and the
- * short-recurrence solvers precondition on the left only: with side right and a
- * preconditioner other than the identity, gk_hh_cycle_start / gk_hh_step_async with
- * precondition = 1 and gk_sr_start return GK_ERR_STATE. */
+ * return GK_ERR_STATE until the next cycle start).  The side is the MGS-R cycle's.
+ * The Householder cycle takes its side per call: GK_HH_PREC_RIGHT preconditions on
+ * the right whatever the context's side is, and GK_HH_PREC_LEFT, like the
+ * short-recurrence solvers, on the left only -- with side right and a preconditioner
+ * other than the identity, gk_hh_cycle_start / gk_hh_step_async with
+ * precondition = GK_HH_PREC_LEFT and gk_sr_start return GK_ERR_STATE. */
 #define GK_SIDE_LEFT 0
 #define GK_SIDE_RIGHT 1
 int gk_set_precond_side(gk_ctx *ctx, int side);
@@ -286,18 +288,43 @@ int gk_update_x(gk_ctx *ctx, const double *y, int n_out);
 int gk_mgs_verr(gk_ctx *ctx, int n_out, int zero_last, double *v_err);
 
 /* -------------------------------------- Householder cycle (gmres_hh.f90) */
-/* Cycle start.  precondition = 0: w = b - A x (gmres_hh_omp :243-253);
- * 1: w = M^-1 (b - A x) (gmres_hh_prec_omp :425-436).  Builds reflector
+/* The `precondition` argument of gk_hh_cycle_start, gk_hh_step and gk_hh_step_async
+ * (any other value: GK_ERR_ARG):
+ *   GK_HH_PREC_NONE   gmres_hh_omp: the operator alone.
+ *   GK_HH_PREC_LEFT   gmres_hh_prec_omp: w = M^-1 A v_j, and |g(j+1)| / ||b|| is the
+ *                     PRECONDITIONED residual over ||b||.  GK_ERR_STATE on a context whose
+ *                     side is right (gk_set_precond_side) with a preconditioner other than
+ *                     the identity.
+ *   GK_HH_PREC_RIGHT  beyond the reference, whatever the context's side is: the cycle
+ *                     starts from w = b - A x, step j forms w = A M^-1 v_j -- ONE launch
+ *                     for cbpr2 on one rank (k_right_cbpr2, GK_TUNE_RIGHT_FUSED), else the
+ *                     preconditioner's launches and the stencil -- and gk_hh_update_x adds
+ *                     M^-1 (P_1..P_n [y;0]), so |g(j+1)| / ||b|| is what gk_true_residual
+ *                     returns, to rounding: the quantity side right gives the MGS-R cycle.
+ *                     The reflection chains, the fused close (GK_TUNE_HH_FUSE),
+ *                     GK_TUNE_RES_FOLD and GK_TUNE_HH_NORM_ORDER apply unchanged.  With
+ *                     the identity preconditioner it runs the launches of GK_HH_PREC_NONE
+ *                     (bit-identical).
+ * A cycle is right-preconditioned or not from its start on: a step whose `precondition`
+ * is GK_HH_PREC_RIGHT in a cycle started otherwise, or the reverse, returns GK_ERR_STATE. */
+#define GK_HH_PREC_NONE 0
+#define GK_HH_PREC_LEFT 1
+#define GK_HH_PREC_RIGHT 2
+/* Cycle start.  GK_HH_PREC_NONE / _RIGHT: w = b - A x (gmres_hh_omp :243-253);
+ * _LEFT: w = M^-1 (b - A x) (gmres_hh_prec_omp :425-436).  Builds reflector
  * P(:,1); returns g1 = g(1) = -sign(beta, w(1)). */
 int gk_hh_cycle_start(gk_ctx *ctx, int precondition, double *g1);
-/* Step j: v = P_1..P_j e_j; w = A v (M^-1 if precondition); w = P_j..P_1 w;
+/* Step j: v = P_1..P_j e_j; w = A v (_LEFT: M^-1 A v; _RIGHT: A M^-1 v); w = P_j..P_1 w;
  * hcol[0..j] = H(1:j+1,j) (H(j+1,j) = -sign(||w(j+1:n)||, w(j+1)));
  * builds P(:,j+1)  (:255-321 / :438-502). */
 int gk_hh_step(gk_ctx *ctx, int j, int precondition, double *hcol);
 /* Split form of gk_hh_step (see gk_mgs_step_async). */
 int gk_hh_step_async(gk_ctx *ctx, int j, int precondition);
 int gk_hh_step_wait(gk_ctx *ctx, int j, double *hcol);
-/* x += P_1..P_n_out [y;0]  (:350-378). */
+/* x += P_1..P_n_out [y;0]  (:350-378); after a cycle started with GK_HH_PREC_RIGHT:
+ * t = P_1..P_n_out [y;0], x += M^-1 t -- for cbpr2 on one rank the cbpr2 sweep with an
+ * accumulating output (t and x read, x written: one launch, GK_TUNE_RIGHT_FUSED), else
+ * the preconditioner's launches into a work vector and the add; bit-identical x. */
 int gk_hh_update_x(gk_ctx *ctx, const double *y, int n_out);
 /* calculate_verr (:568-593): v_err(i) = sum_{j<i} 2 (V_i.V_j)^2, V rebuilt
  * from the reflectors on device (extra n x n_out buffer). */
@@ -569,7 +596,10 @@ int gk_res_info(gk_ctx *ctx, int hh, long long *info);
  *                          one two-level line march (k_right_cbpr2: v and the dot partner
  *                          read, w written, z = M^-1 v never stored); 0: the route of N ranks
  *                          and of Chebyshev(k) -- the preconditioner's launch, then the
- *                          stencil.  Bit-identical w
+ *                          stencil.  Bit-identical w.  The same key selects the update of a
+ *                          GK_HH_PREC_RIGHT cycle (gk_hh_update_x): 1 the cbpr2 sweep with the
+ *                          accumulating output, x += M^-1 t in one launch; 0 the sweep into a
+ *                          work vector, then the add.  Bit-identical x
  *   GK_TUNE_SPIN_WAIT      1 (default): gk_mgs_step_wait / gk_hh_step_wait spin on the step's
  *                          event; 0: hipEventSynchronize (may sleep in the driver per step) */
 #define GK_TUNE_PROJ_NT 0
