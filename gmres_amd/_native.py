@@ -24,6 +24,7 @@ HEADER = os.path.join(os.path.dirname(PKG), "include", "gmres_hip.h")
 GK_OK = 0
 GK_ERR_COMM = -6
 GK_TUNE_PROJ_NT = 0
+GK_TUNE_PROJ_BLOCKS = 1
 GK_TUNE_STENCIL_BLOCKS = 2
 GK_TUNE_SR_BLOCKS = 28
 GK_TUNE_SR_TWO_LEVEL = 29
@@ -46,6 +47,8 @@ GK_TUNE_RIGHT_FUSED = 31
 GK_TUNE_RES_PIPE_CARRY = 32
 GK_SIDE_LEFT, GK_SIDE_RIGHT = 0, 1
 GK_BASIS_F64, GK_BASIS_F32 = 0, 1
+GK_ORTH_MGSR, GK_ORTH_CGS2 = 0, 1
+GK_CGS_KB = 8  # columns a dots workgroup of the CGS2 step batches (GK_CGS_KB=16 in gk_create's environment: 16)
 GK_HH_PREC_NONE, GK_HH_PREC_LEFT, GK_HH_PREC_RIGHT = 0, 1, 2
 GK_ERR_ARG, GK_ERR_STATE = -1, -4
 GK_PREC_IDENTITY, GK_PREC_CBPR2, GK_PREC_CHEB = 0, 1, 2
@@ -111,6 +114,8 @@ _SIGS = {
     "gk_set_basis_precision": (c_int, [c_vp, c_int]),
     "gk_get_basis_precision": (c_int, [c_vp, _ip]),
     "gk_cb_plan_query": (c_int, [c_ll, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
+    "gk_set_orthogonalization": (c_int, [c_vp, c_int]),
+    "gk_get_orthogonalization": (c_int, [c_vp, _ip]),
     "gk_set_rhs": (c_int, [c_vp, _dp]),
     "gk_set_rhs_ones": (c_int, [c_vp]),
     "gk_rhs_norm": (c_int, [c_vp, _dp]),

@@ -34,7 +34,7 @@ DRIVER = os.path.join(LIB, "test_mfp_hip")
 # gk_cheb0..3 26-31, gk_blk 15, gk_resident 42-48 (the unrolled resident kernels),
 # gk_comm 4, gk_sr_api 8; the single gk_api unit they were split from took 47-60.
 HIP_SOURCES = [os.path.join(CSRC, f) for f in ("gk_api.hip", "gk_cheb.hip", "gk_blk.hip", "gk_resident.hip",
-                                                "gk_comm.hip", "gk_sr_api.hip", "gk_cb.hip")]
+                                                "gk_comm.hip", "gk_sr_api.hip", "gk_cb.hip", "gk_cgs.hip")]
 # (source, extra defines, object name): the Chebyshev pass in GK_CF_PARTS parts
 GK_CF_PARTS = 4
 HIP_UNITS = ([(HIP_SOURCES[0], [], "gk_api.o")] + [(HIP_SOURCES[1], [f"GK_CF_PART={p}"], f"gk_cheb{p}.o")
@@ -44,9 +44,11 @@ HIP_UNITS = ([(HIP_SOURCES[0], [], "gk_api.o")] + [(HIP_SOURCES[1], [f"GK_CF_PAR
 # launch-path projection, x update and Gram are float instantiations in gk_api's unit); HIP_UNITS stays
 # the FP64 solvers' list
 HIP_UNITS_CB = [(HIP_SOURCES[6], [], "gk_cb.o")]
+# ... and the unit of the opt-in CGS2 Arnoldi step (batched dots, reduce, j-column AXPY): eleven in all
+HIP_UNITS_CGS = [(HIP_SOURCES[7], [], "gk_cgs.o")]
 HIP_HEADERS = [os.path.join(CSRC, h) for h in ("gk_common.hpp", "gk_kernels.hpp", "gk_cheb.hpp", "gk_res.hpp",
                                                 "gk_blk.hpp", "gk_sr.hpp", "gk_host.hpp", "gk_resident.hpp",
-                                                "gk_cb.hpp")]
+                                                "gk_cb.hpp", "gk_cgs.hpp")]
 HIP_DEPS = HIP_SOURCES + HIP_HEADERS + [os.path.join(ROOT, "include", "gmres_hip.h")]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall"]
 F_SOURCES = [os.path.join(FSRC, "gmres_hip.f90")]
@@ -100,7 +102,7 @@ def _compile_link(so: str, defines: list[str]) -> None:
     pass at run time; a spilled resident kernel holds w in scratch memory): the
     build fails here, naming them."""
     objs, procs = [], []
-    for src, unit_defs, oname in HIP_UNITS + HIP_UNITS_CB:
+    for src, unit_defs, oname in HIP_UNITS + HIP_UNITS_CB + HIP_UNITS_CGS:
         obj = os.path.join(os.path.dirname(so), oname)
         cmd = [hipcc(), *HIP_FLAGS, *[f"-D{x}" for x in defines + unit_defs], "-c", src, "-o", obj,
                "-Rpass-analysis=kernel-resource-usage"]
@@ -112,7 +114,7 @@ def _compile_link(so: str, defines: list[str]) -> None:
         err = p.communicate()[1]
         sys.stderr.write("".join(l + "\n" for l in err.splitlines() if "warning:" in l or "error" in l))
         for name in ("k_cheb_fused", "k_mgs_wpc", "k_mgs_wres", "k_mgs_res", "k_mgs_blk", "k_right_cbpr2",
-                     "k_mgs_wcb", "k_stencil"):
+                     "k_mgs_wcb", "k_stencil", "k_cgs_"):
             bad += _scratch_kernels(err, name)
     if any(p.returncode for p in procs):
         raise subprocess.CalledProcessError(max(p.returncode for p in procs), "hipcc")

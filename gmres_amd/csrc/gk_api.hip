@@ -23,6 +23,7 @@
 
 #include "gk_blk.hpp"
 #include "gk_cb.hpp"
+#include "gk_cgs.hpp"
 #include "gk_host.hpp"
 #include "gk_kernels.hpp"
 #include "gk_resident.hpp"
@@ -899,7 +900,57 @@ int mgs_chain_t(gk_ctx *c, int j, int np) {
     return scale_col(c, j, slot(c, s0), np, hs + j, c->hallh_dev + (i64)(j - 1) * m2, hs, j);
 }
 
+// The CGS2 step's buffers, allocated at its first use: the dots' partial slab (m rows of
+// np_pj workgroups) and s (m doubles).  A slab grown for a larger workgroup count drops the
+// captured steps, which hold its address.
+int ensure_cgs(gk_ctx *c) {
+    const i64 need = (i64)c->m * c->np_pj;
+    if (c->cgs_slab == nullptr || c->cgs_cap < need) {
+        graph_reset(c);
+        if (c->cgs_slab != nullptr) HIPCHK(hipFree(c->cgs_slab));
+        c->cgs_slab = nullptr;
+        c->cgs_cap = 0;
+        HIPCHK(hipMalloc(&c->cgs_slab, sizeof(double) * (size_t)need));
+        c->cgs_cap = need;
+    }
+    if (c->cgs_s == nullptr) HIPCHK(hipMalloc(&c->cgs_s, sizeof(double) * (size_t)c->m));
+    return GK_OK;
+}
+
+// The CGS2 cascade of step j (gk_set_orthogonalization GK_ORTH_CGS2, gk_cgs.hpp) after the
+// operator launch: two sweeps of batched dots on the same w, their fixed-order reduce, the
+// all-reduce of s and the j-column AXPY (the second also leaves the partials of ||w||^2),
+// then the MGS-R step's closing.  7 launches and 3 all-reduces whatever j is.
+int cgs_chain(gk_ctx *c, int j) {
+    const int m2 = c->m + 2, G = c->np_pj;
+    double *hs = c->hall + (i64)(j - 1) * m2;
+    const bool nt = c->tune_nt > 0 || (c->tune_nt < 0 && c->nt_auto);
+    if (c->cgs_slab == nullptr || c->cgs_s == nullptr || c->cgs_cap < (i64)j * G)
+        return set_err(GK_ERR_STATE, "CGS2 step %d without its buffers", j);
+    for (int sweep = 0; sweep < 2; ++sweep) {
+        {
+            ProfScope ps(c, GK_KID_PROJ);
+            HIPCHK(gk::cgs_dots(c->cgs_kb, nt, G, c->w, c->V, c->ld, j, c->nloc, c->cgs_slab, c->st));
+        }
+        {
+            ProfScope ps(c, GK_KID_OTHER);
+            HIPCHK(gk::cgs_reduce(c->cgs_slab, G, j, c->cgs_s, c->st));
+        }
+        CHK(allreduce(c, c->cgs_s, j, true));
+        {
+            ProfScope ps(c, GK_KID_PROJ);
+            HIPCHK(gk::cgs_axpy(sweep == 1, nt, G, c->w, c->V, c->ld, j, c->nloc, c->cgs_s, hs, sweep == 0, slot(c, 0),
+                                c->st));
+        }
+    }
+    CHK(allreduce(c, slot(c, 0), G));
+    return scale_col(c, j, slot(c, 0), G, hs + j, c->hallh_dev + (i64)(j - 1) * m2, hs, j);
+}
+
+// The launch-path chain of step j the context's scheme selects (np: the first dot's partials,
+// which the CGS2 chain does not consume).
 int mgs_chain(gk_ctx *c, int j, int np) {
+    if (cgs_on(c)) return cgs_chain(c, j);
     return cb_on(c) ? mgs_chain_t<float>(c, j, np) : mgs_chain_t<double>(c, j, np);
 }
 
@@ -981,8 +1032,15 @@ int gk_create(int device, int nside, int line0, int nlines, int m, gk_ctx **out)
     *out = nullptr;
     if (nside < 2 || nlines < 1 || line0 < 0 || line0 + nlines > nside || m < 1 || m > 4096)
         return set_err(GK_ERR_ARG, "bad shape N=%d line0=%d nlines=%d m=%d", nside, line0, nlines, m);
+    // GK_CGS_KB (environment, read here): columns a dots workgroup of the CGS2 step batches, for A/B runs
+    int cgs_kb = gk::CGS_KB_DEFAULT;
+    if (const char *kb = std::getenv("GK_CGS_KB")) {
+        cgs_kb = std::atoi(kb);
+        if (cgs_kb != 8 && cgs_kb != 16) return set_err(GK_ERR_ARG, "GK_CGS_KB=%s: batches of 8 or 16 columns", kb);
+    }
     HIPCHK(hipSetDevice(device));
     gk_ctx *c = new gk_ctx();
+    c->cgs_kb = cgs_kb;
     c->dev = device;
     c->N = nside;
     c->line0 = line0;
@@ -1087,7 +1145,7 @@ int gk_destroy(gk_ctx *c) {
     for (hipEvent_t e : c->sr_pend) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->sr_evfree) (void)hipEventDestroy(e);
     double *bufs[] = {c->V, c->w, c->z, c->aux, c->dA, c->dB, c->x, c->b, c->vj, c->hlo, c->hhi, c->dh, c->zline,
-                      c->red, c->hcol, c->ydev, c->hb, c->scal, c->Vb, c->gram_slab, c->gram_out};
+                      c->red, c->hcol, c->ydev, c->hb, c->scal, c->Vb, c->gram_slab, c->gram_out, c->cgs_slab, c->cgs_s};
     for (double *p : bufs)
         if (p) (void)hipFree(p);
     if (c->gram_pairs) (void)hipFree(c->gram_pairs);
@@ -1147,6 +1205,7 @@ int gk_set_basis_precision(gk_ctx *c, int prec) {
         if (c->nranks > 1 || c->comm != nullptr || c->lg != nullptr)
             return set_err(GK_ERR_STATE, "the FP32 basis needs a single-rank context (no communicator)");
         if (c->m < 3) return set_err(GK_ERR_ARG, "the FP32 basis needs m >= 3 (m = %d)", c->m);
+        if (cgs_on(c)) return set_err(GK_ERR_STATE, "the FP32 basis has no CGS2 step: set GK_ORTH_MGSR first");
     }
     sr_invalidate(c);
     c->cycle_mgs = c->cycle_hh = false;  // the open cycle's basis is stored in the other format
@@ -1159,6 +1218,25 @@ int gk_get_basis_precision(gk_ctx *c, int *prec) {
     CHK(check_ctx(c));
     if (prec == nullptr) return set_err(GK_ERR_ARG, "null prec");
     *prec = c->basis;
+    return GK_OK;
+}
+
+int gk_set_orthogonalization(gk_ctx *c, int scheme) {
+    CHK(check_ctx(c));
+    if (scheme != GK_ORTH_MGSR && scheme != GK_ORTH_CGS2) return set_err(GK_ERR_ARG, "bad orthogonalization %d", scheme);
+    if (scheme == GK_ORTH_CGS2 && cb_on(c))
+        return set_err(GK_ERR_STATE, "the CGS2 step runs on FP64 columns: set GK_BASIS_F64 first");
+    sr_invalidate(c);
+    c->cycle_mgs = c->cycle_hh = false;  // the open cycle's columns were made by the other scheme
+    if (scheme != c->orth) graph_reset(c);  // the captured steps are the other scheme's chains
+    c->orth = scheme;
+    return GK_OK;
+}
+
+int gk_get_orthogonalization(gk_ctx *c, int *scheme) {
+    CHK(check_ctx(c));
+    if (scheme == nullptr) return set_err(GK_ERR_ARG, "null scheme");
+    *scheme = c->orth;
     return GK_OK;
 }
 
@@ -1344,15 +1422,20 @@ int gk_mgs_step_async(gk_ctx *c, int j) {
     ResPlan rp;
     gk::CbPlan cp;
     const bool cb = cb_on(c);
-    const bool res = cb ? cb_plan_ctx(c, cp) : res_plan(c, rp);
+    const bool cgs = cgs_on(c);  // its chain runs launch by launch (or as a graph): never a resident launch
+    const bool res = cgs ? false : (cb ? cb_plan_ctx(c, cp) : res_plan(c, rp));
+    if (cgs) CHK(ensure_cgs(c));
+    // The CGS2 sweeps take every dot themselves: no fused first dot, except where the operator
+    // route is chosen by it (Chebyshev on the left, op_precond_sten) -- its slab stays unconsumed.
+    const int acc = cgs && !(c->pkind == GK_PREC_CHEB && !right_prec(c)) ? gk::ACC_NONE : gk::ACC_DOT;
     // the operator's input V(:,j) and the first dot's partner V(:,1); compressed basis: their
     // widened copies (the operator stage itself is the same launches)
     const double *vj = cb ? cb_vjw(c) : V + (i64)(j - 1) * ld, *v1 = cb ? cb_v1w(c) : V;
     // w = M^-1 A V(:,j) (side right: A M^-1 V(:,j)), fused with the first dot <w, V(:,1)>
     if (right_prec(c))
-        CHK(op_right(c, vj, c->w, gk::ACC_DOT, v1, slot(c, s0)));
+        CHK(op_right(c, vj, c->w, acc, v1, slot(c, s0)));
     else
-        CHK(op_precond(c, vj, c->w, false, gk::ACC_DOT, v1, slot(c, s0)));
+        CHK(op_precond(c, vj, c->w, false, acc, v1, slot(c, s0)));
     int np = c->last_np;
     if (res) {  // the whole cascade + norm + scale as one resident launch
         // N ranks on the device exchange: the first dot's rank totals inside the launch
@@ -1993,7 +2076,7 @@ int gk_res_info(gk_ctx *c, int hh, long long *info) {
     CHK(check_ctx(c));
     if (info == nullptr) return set_err(GK_ERR_ARG, "null info");
     ResPlan p;
-    const bool on = res_plan(c, p, hh != 0);
+    const bool on = !(hh == 0 && cgs_on(c)) && res_plan(c, p, hh != 0);  // a CGS2 context's MGS step: launch by launch
     plan_info(p, on, info);
     if (cb_on(c) && hh == 0) {  // the MGS-R step of a compressed-basis context: k_mgs_wcb's plan
         gk::CbPlan cp;

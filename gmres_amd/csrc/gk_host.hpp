@@ -66,6 +66,10 @@ struct gk_ctx {
     int side = GK_SIDE_LEFT;   // MGS-R: left (the reference) or right preconditioning (gk_set_precond_side)
     int tune_right_fused = 1;  // side right, cbpr2, one rank: w = A M^-1 v as one march (k_right_cbpr2)
     int basis = GK_BASIS_F64;  // MGS-R: storage precision of the Krylov columns (gk_set_basis_precision, gk_cb.hpp)
+    int orth = GK_ORTH_MGSR;   // MGS-R cycle: the step's orthogonalisation (gk_set_orthogonalization, gk_cgs.hpp)
+    int cgs_kb = 8;            // CGS2: columns a dots workgroup batches (gk_create: GK_CGS_KB in the environment)
+    double *cgs_slab = nullptr, *cgs_s = nullptr;  // CGS2 (lazy): the dots' partials [m][np_pj], s[m]
+    i64 cgs_cap = 0;                               // doubles cgs_slab holds
     // decomposition / comm
     int nranks = 1, rank = 0, max_lines = 0;
     int min_lines = 0;  // smallest slab of any rank (0: not gathered yet; ensure_min_lines)
@@ -212,6 +216,8 @@ inline bool right_prec(const gk_ctx *c) { return c->side == GK_SIDE_RIGHT && c->
 // Compressed basis (gk_cb.hpp): the FP32 columns in the lower half of V, the two widened
 // FP64 vectors the operator stage reads in its last two double columns.
 inline bool cb_on(const gk_ctx *c) { return c->basis == GK_BASIS_F32; }
+// The MGS-R cycle steps by CGS2 (gk_set_orthogonalization; FP64 columns only, gk_cgs.hpp)
+inline bool cgs_on(const gk_ctx *c) { return c->orth == GK_ORTH_CGS2; }
 template <class T>  // column k (0-based) of the MGS-R basis in the type T it is stored in
 inline T *vcol(const gk_ctx *c, int k) { return reinterpret_cast<T *>(c->V) + (i64)k * c->ld; }
 inline double *cb_v1w(const gk_ctx *c) { return c->V + (i64)(c->m - 1) * c->ld; }

@@ -26,6 +26,7 @@ module gmres_hip_c
     integer(c_int), parameter :: GK_PREC_IDENTITY = 0, GK_PREC_CBPR2 = 1, GK_PREC_CHEB = 2
     integer(c_int), parameter :: GK_SIDE_LEFT = 0, GK_SIDE_RIGHT = 1
     integer(c_int), parameter :: GK_BASIS_F64 = 0, GK_BASIS_F32 = 1
+    integer(c_int), parameter :: GK_ORTH_MGSR = 0, GK_ORTH_CGS2 = 1
     integer(c_int), parameter :: GK_HH_PREC_NONE = 0, GK_HH_PREC_LEFT = 1, GK_HH_PREC_RIGHT = 2
     integer(c_int), parameter :: GK_VEC_X = 0, GK_VEC_B = 1
     integer(c_int), parameter :: GK_SR_PCG = 0, GK_SR_BICGSTAB = 1
@@ -69,6 +70,16 @@ module gmres_hip_c
             import :: c_ptr, c_int
             type(c_ptr), value :: ctx
             integer(c_int), intent(out) :: prec
+        end function
+        integer(c_int) function gk_set_orthogonalization(ctx, scheme) bind(C, name='gk_set_orthogonalization')
+            import :: c_ptr, c_int
+            type(c_ptr), value :: ctx
+            integer(c_int), value :: scheme
+        end function
+        integer(c_int) function gk_get_orthogonalization(ctx, scheme) bind(C, name='gk_get_orthogonalization')
+            import :: c_ptr, c_int
+            type(c_ptr), value :: ctx
+            integer(c_int), intent(out) :: scheme
         end function
         integer(c_int) function gk_set_rhs(ctx, b) bind(C, name='gk_set_rhs')
             import :: c_int, c_ptr, c_double
@@ -309,7 +320,7 @@ module gmres_hip
     integer, parameter, public :: MGSR_OMP = 1, MGSR_MF = 0
 
     public :: stencil_vector, precond
-    public :: GK_SIDE_LEFT, GK_SIDE_RIGHT, GK_BASIS_F64, GK_BASIS_F32
+    public :: GK_SIDE_LEFT, GK_SIDE_RIGHT, GK_BASIS_F64, GK_BASIS_F32, GK_ORTH_MGSR, GK_ORTH_CGS2
     public :: GK_HH_PREC_NONE, GK_HH_PREC_LEFT, GK_HH_PREC_RIGHT
     public :: hip_poisson5, hip_identity, hip_cbpr2, hip_chebyshev
     public :: gmres_mgsr_hip, gmres_hh_hip, gmres_hh_prec_hip, hip_release
@@ -889,9 +900,12 @@ contains
     !> x += M^-1 V y): final_err(j) is then the true relative residual, where the
     !> reference's left side reports ||M^-1 (b - A x)|| / ||b||.  Optional
     !> basis = GK_BASIS_F32 stores the Krylov columns as FP32 (gk_set_basis_precision:
-    !> everything else stays FP64, the solve still converges to FP64 accuracy).
+    !> everything else stays FP64, the solve still converges to FP64 accuracy).  Optional
+    !> orth = GK_ORTH_CGS2 orthogonalises each Arnoldi step by classical Gram-Schmidt with
+    !> one full reorthogonalisation (gk_set_orthogonalization: batched dots, three
+    !> reductions per step; FP64 columns only).
     subroutine gmres_mgsr_hip(Ax_vec, b, x, m, tol, final_err, v_err, n_out, restart_out, M_inv, params, variant, &
-                              side, basis)
+                              side, basis, orth)
         procedure(stencil_vector) :: Ax_vec
         real(8), intent(in) :: b(:)
         real(8), allocatable, intent(out) :: x(:)
@@ -901,7 +915,7 @@ contains
         integer, intent(out) :: n_out, restart_out
         procedure(precond) :: M_inv
         real(8), intent(in) :: params(:)
-        integer, intent(in), optional :: variant, side, basis
+        integer, intent(in), optional :: variant, side, basis, orth
         type(c_ptr) :: ctx
         integer(c_int) :: kind, degree, sd
         integer :: var, ncyc
@@ -915,6 +929,7 @@ contains
         allocate (x(size(b)), final_err(m), v_err(m + 1))
         ctx = solver_ctx(b, m, kind, degree, params, sd)
         if (present(basis)) call gk_require(gk_set_basis_precision(ctx, int(basis, c_int)), 'gk_set_basis_precision')
+        if (present(orth)) call gk_require(gk_set_orthogonalization(ctx, int(orth, c_int)), 'gk_set_orthogonalization')
         call gk_require(mgsr_drive(ctx, m, tol, norm2(b), var, hip_max_restarts, x, final_err, v_err, n_out, &
                                    restart_out, .true., .false., dummy_h, dummy_f, ncyc), 'gmres_mgsr_hip')
         call gk_require(gk_destroy(ctx), 'gk_destroy')

@@ -7,7 +7,8 @@
 !! An optional third argument `right` runs the MGS-R solve alone, preconditioned
 !! on the right (side = GK_SIDE_RIGHT: its "Final residual" is the true one); `f32`
 !! runs it alone on the compressed basis (basis = GK_BASIS_F32: the Krylov columns
-!! stored as FP32); `hhright` runs the Householder solve alone, preconditioned on the
+!! stored as FP32); `cgs2` runs it alone with the CGS2 Arnoldi step (orth = GK_ORTH_CGS2);
+!! `hhright` runs the Householder solve alone, preconditioned on the
 !! right (gmres_hh_prec_hip(..., side = GK_SIDE_RIGHT)), and prints its final residual
 !! a second time with every digit.
 program test_mfp_hip
@@ -15,17 +16,18 @@ program test_mfp_hip
     implicit none
     integer :: nsize, max_iter, n_args
     character(len=32) :: arg_str
-    logical :: right, f32, hhright
+    logical :: right, f32, hhright, cgs2
     n_args = command_argument_count()
     if (n_args < 2) then
-        print *, "usage ./test_mfp_hip <grid size> <iterations per restart> [right|f32|hhright]"
+        print *, "usage ./test_mfp_hip <grid size> <iterations per restart> [right|f32|cgs2|hhright]"
         stop
     end if
-    right = .false.; f32 = .false.; hhright = .false.
+    right = .false.; f32 = .false.; hhright = .false.; cgs2 = .false.
     if (n_args >= 3) then
         call get_command_argument(3, arg_str)
         right = trim(arg_str) == 'right'
         f32 = trim(arg_str) == 'f32'
+        cgs2 = trim(arg_str) == 'cgs2'
         hhright = trim(arg_str) == 'hhright'
     end if
     call get_command_argument(1, arg_str)
@@ -33,7 +35,7 @@ program test_mfp_hip
     call get_command_argument(2, arg_str)
     read (arg_str, *) max_iter
     write (*, '(60("-"))')
-    if (.not. right .and. .not. f32) then
+    if (.not. right .and. .not. f32 .and. .not. cgs2) then
         call run(nsize, max_iter, .true.)
         write (*, '(60("-"))')
     end if
@@ -62,6 +64,8 @@ contains
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR Chebyshev on the right, MI355X)'
         else if (f32) then
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR Chebyshev, compressed basis, MI355X)'
+        else if (cgs2) then
+            write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (CGS2 Chebyshev, MI355X)'
         else
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR Chebyshev, MI355X)'
         end if
@@ -78,6 +82,9 @@ contains
         else if (f32) then
             call gmres_mgsr_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params, &
                                 basis=GK_BASIS_F32)
+        else if (cgs2) then
+            call gmres_mgsr_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params, &
+                                orth=GK_ORTH_CGS2)
         else
             call gmres_mgsr_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params)
         end if

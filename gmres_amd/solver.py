@@ -21,6 +21,7 @@ PREC = {"identity": nat.GK_PREC_IDENTITY, "none": nat.GK_PREC_IDENTITY,
         "cbpr2": nat.GK_PREC_CBPR2, "cheb": nat.GK_PREC_CHEB, "chebyshev": nat.GK_PREC_CHEB}
 SIDE = {"left": nat.GK_SIDE_LEFT, "right": nat.GK_SIDE_RIGHT}
 BASIS = {"f64": nat.GK_BASIS_F64, "f32": nat.GK_BASIS_F32}
+ORTH = {"mgsr": nat.GK_ORTH_MGSR, "cgs2": nat.GK_ORTH_CGS2}
 HH_PREC = {"none": nat.GK_HH_PREC_NONE, "left": nat.GK_HH_PREC_LEFT, "right": nat.GK_HH_PREC_RIGHT}
 MGSR_MF, MGSR_OMP = 0, 1
 
@@ -215,6 +216,21 @@ class Context:
         v = ctypes.c_int()
         nat.check(nat.hip().gk_get_basis_precision(self._h, ctypes.byref(v)), "gk_get_basis_precision")
         return {b: a for a, b in BASIS.items()}[v.value]
+
+    def set_orth(self, orth: str = "mgsr") -> None:
+        """Orthogonalisation of the MGS-R cycle's Arnoldi step (gk_set_orthogonalization):
+        "mgsr" (default, the reference) or "cgs2" -- classical Gram-Schmidt with one full
+        reorthogonalisation: batched dots, three reductions per step whatever j is, on every
+        communicator and for every m; FP64 columns only.  Ends an open cycle."""
+        if orth not in ORTH:
+            raise ValueError(f"orth must be 'mgsr' or 'cgs2', not {orth!r}")
+        nat.check(nat.hip().gk_set_orthogonalization(self._h, ORTH[orth]), "gk_set_orthogonalization")
+
+    @property
+    def orth(self) -> str:
+        v = ctypes.c_int()
+        nat.check(nat.hip().gk_get_orthogonalization(self._h, ctypes.byref(v)), "gk_get_orthogonalization")
+        return {b: a for a, b in ORTH.items()}[v.value]
 
     def set_rhs(self, b_local: np.ndarray) -> None:
         b = np.ascontiguousarray(b_local, dtype=np.float64).reshape(-1)

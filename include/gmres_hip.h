@@ -227,6 +227,40 @@ int gk_set_precond_side(gk_ctx *ctx, int side);
 int gk_set_basis_precision(gk_ctx *ctx, int prec);
 int gk_get_basis_precision(gk_ctx *ctx, int *prec);
 int gk_cb_plan_query(long long nloc, int cus, int share, int m, long long *info);
+/* Orthogonalisation scheme of the MGS-R cycle's Arnoldi step (context state; default
+ * GK_ORTH_MGSR; kept across gk_set_precond, gk_set_precond_side and gk_set_tuning).
+ *   GK_ORTH_MGSR  modified Gram-Schmidt with one reorthogonalisation, the reference
+ *                 (gmres_mgsr.f90:341-360): 2j dependent dots per step.
+ *   GK_ORTH_CGS2  classical Gram-Schmidt with one full reorthogonalisation (beyond the
+ *                 reference; it changes the operation order, so it is opt-in).  After the
+ *                 unchanged operator stage, step j runs two sweeps of
+ *                     s_k = <w, V_k>, k = 1..j, every dot on the SAME w (N ranks: rank totals)
+ *                     w_e = ((w_e - s_1 V_1,e) - s_2 V_2,e) .. - s_j V_j,e   (k ascending)
+ *                     H(k,j) = s_k (sweep 1)  /  H(k,j) + s_k (sweep 2)
+ *                 then h = ||w||, V(:,j+1) = w / h as in the MGS-R step (h = 0 writes zeros).
+ *                 Three reductions per step whatever j is: 7 launches (batched dots, their
+ *                 fixed-order reduce, the j-column AXPY; twice; the scale) and 3 all-reduces
+ *                 against the launch path's 2j + 1 of each.  No in-launch waiting, so it runs
+ *                 on every communicator and for every m.  The MGS step of a CGS2 context
+ *                 never runs a resident launch: gk_res_info(hh = 0) reports GK_RES_NONE, and
+ *                 GK_TUNE_RES, GK_TUNE_RES_BLOCK and GK_TUNE_RES_PF are ignored for it (they
+ *                 keep their values for when GK_ORTH_MGSR comes back).  GK_TUNE_GRAPH,
+ *                 GK_TUNE_PROJ_NT and GK_TUNE_PROJ_BLOCKS apply.  A dots workgroup batches 8
+ *                 columns against each load of w; GK_CGS_KB=16 in the environment of
+ *                 gk_create builds the context on batches of 16 (an A/B knob: any other
+ *                 value is GK_ERR_ARG).  The Householder cycle, gk_sr_* and
+ *                 gk_vec_* are unaffected.  FP64 columns only: GK_ORTH_CGS2 on a
+ *                 GK_BASIS_F32 context and gk_set_basis_precision(GK_BASIS_F32) on a
+ *                 GK_ORTH_CGS2 context return GK_ERR_STATE (a float-column instantiation
+ *                 of the three kernels is the natural follow-up).
+ * Any other value returns GK_ERR_ARG.  Setting the scheme ends a running gk_sr_* solve and
+ * an open GMRES cycle (steps return GK_ERR_STATE until the next gk_mgs_cycle_start) and
+ * drops the captured step graphs, as gk_set_basis_precision does.  Setting GK_ORTH_MGSR
+ * again gives back the default solve bit for bit. */
+#define GK_ORTH_MGSR 0   /* the reference: gmres_mgsr.f90:341-360 (default) */
+#define GK_ORTH_CGS2 1   /* beyond the reference */
+int gk_set_orthogonalization(gk_ctx *ctx, int scheme);
+int gk_get_orthogonalization(gk_ctx *ctx, int *scheme);
 /* Right-hand side b (local part, host) or b = A*1 built on device
  * (the manufactured RHS of every reference driver, test_poisson_mf.f90:39-40). */
 int gk_set_rhs(gk_ctx *ctx, const double *b_local);
