@@ -1,6 +1,6 @@
 // gk_api.hip -- C-ABI implementation of include/gmres_hip.h (libgmres_hip.so): the
-// context, the operator / preconditioner launches, the Arnoldi steps, tuning and
-// profiling.  The collectives live in gk_comm.hip, the resident step's kernels,
+// context, the Arnoldi steps, tuning and profiling.  The operator and the preconditioner
+// live in gk_op.hip, the collectives in gk_comm.hip, the resident step's kernels,
 // planner and launchers in gk_resident.hip (the blocked step in gk_blk.hip), the
 // short-recurrence solvers in gk_sr_api.hip; gk_host.hpp is what they share.
 //
@@ -129,95 +129,6 @@ void set_geometry(gk_ctx *c) {
 }
 
 // -------------------------------------------------------------- launches ---
-template <int VEC, int OP, int ACC>
-int launch_stencil_v(gk_ctx *c, const gk::StArgs &a) {
-    gk::k_stencil<VEC, OP, ACC><<<c->sgrid, gk::TPB, 0, c->st>>>(a);
-    LAUNCHCHK();
-    return GK_OK;
-}
-
-template <int OP, int ACC>
-int launch_stencil_o(gk_ctx *c, const gk::StArgs &a) {
-    return c->vec == 2 ? launch_stencil_v<2, OP, ACC>(c, a) : launch_stencil_v<1, OP, ACC>(c, a);
-}
-
-template <int OP>
-int launch_stencil_a(gk_ctx *c, int acc, const gk::StArgs &a) {
-    if (acc == gk::ACC_NONE) return launch_stencil_o<OP, gk::ACC_NONE>(c, a);
-    if (acc == gk::ACC_DOT) return launch_stencil_o<OP, gk::ACC_DOT>(c, a);
-    return launch_stencil_o<OP, gk::ACC_NORM>(c, a);
-}
-
-int stencil(gk_ctx *c, int op, int acc, gk::StArgs a) {
-    ProfScope ps(c, GK_KID_STENCIL);
-    if (acc != gk::ACC_NONE) c->last_np = c->np_st;
-    a.hlo = halo_lo(c);
-    a.hhi = halo_hi(c);
-    a.N = c->N;
-    a.nlines = c->nlines;
-    a.JT = c->JT;
-    switch (op) {
-        case gk::OP_PLAIN: return launch_stencil_a<gk::OP_PLAIN>(c, acc, a);
-        case gk::OP_RESID: return launch_stencil_a<gk::OP_RESID>(c, acc, a);
-        case gk::OP_CBPR2: return launch_stencil_a<gk::OP_CBPR2>(c, acc, a);
-        case gk::OP_CHEB_FIRST: return launch_stencil_a<gk::OP_CHEB_FIRST>(c, acc, a);
-        case gk::OP_CBPR2_ADD:  // the update's accumulate form carries no reduction
-            if (acc != gk::ACC_NONE) return set_err(GK_ERR_ARG, "OP_CBPR2_ADD: reduction %d", acc);
-            return launch_stencil_o<gk::OP_CBPR2_ADD, gk::ACC_NONE>(c, a);
-        default: return launch_stencil_a<gk::OP_CHEB_ITER>(c, acc, a);
-    }
-}
-
-// cbpr2 coefficients exactly as chebyshev.f90:19-25
-void cbpr2_coefs(const gk_ctx *c, double *d_out, double *alpha_out) {
-    const double em = c->p0, eM = c->p1;
-    const double cc = (eM - em) / 2.0;
-    const double d = (eM + em) / 2.0;
-    double alpha = 1.0 / d;
-    double beta = cc * alpha / 2.0;
-    beta = beta * beta;
-    alpha = 1.0 / (d - beta);
-    *d_out = d;
-    *alpha_out = alpha;
-}
-
-// The one-launch route of w = A (M^-1 v) (gk::k_right_cbpr2): cbpr2 on one rank
-// that holds the whole grid -- the march has no halo lines, the level-1 value of a
-// neighbour's line would need two of its lines.  Everything else takes the
-// two-launch route (GK_TUNE_RIGHT_FUSED 0 forces it).
-bool right_fused_ok(const gk_ctx *c) {
-    return c->tune_right_fused != 0 && c->pkind == GK_PREC_CBPR2 && c->nranks == 1 && c->line0 == 0 &&
-           c->nlines == c->N;
-}
-
-template <int VEC>
-int launch_right_v(gk_ctx *c, int acc, const gk::RcArgs &a) {
-    if (acc == gk::ACC_DOT)
-        gk::k_right_cbpr2<VEC, gk::ACC_DOT><<<c->sgrid, gk::TPB, 0, c->st>>>(a);
-    else
-        gk::k_right_cbpr2<VEC, gk::ACC_NONE><<<c->sgrid, gk::TPB, 0, c->st>>>(a);
-    LAUNCHCHK();
-    return GK_OK;
-}
-
-// out = A (cbpr2 v) in one launch; acc = ACC_DOT leaves <out, vdot> in slab `part`
-// (np_st partials, k_stencil's layout).
-int right_cbpr2(gk_ctx *c, const double *v, double *out, int acc, const double *vdot, double *part) {
-    if (acc != gk::ACC_NONE && acc != gk::ACC_DOT) return set_err(GK_ERR_ARG, "right_cbpr2: reduction %d", acc);
-    ProfScope ps(c, GK_KID_STENCIL);
-    if (acc != gk::ACC_NONE) c->last_np = c->np_st;
-    gk::RcArgs a{};
-    a.v = v;
-    a.w = out;
-    a.vdot = vdot;
-    a.part = part;
-    cbpr2_coefs(c, &a.d, &a.alpha);
-    a.N = c->N;
-    a.nlines = c->nlines;
-    a.JT = c->JT;
-    return c->vec == 2 ? launch_right_v<2>(c, acc, a) : launch_right_v<1>(c, acc, a);
-}
-
 // T: the type va / vb are stored in (float: the FP32 basis, PJ_AXPY_DOT / PJ_AXPY_NORM only)
 template <bool NT, int U, class T>
 void launch_proj_u(gk_ctx *c, int mode, double *w, const T *va, const T *vb, const double *pin, int npin,
@@ -299,6 +210,14 @@ template <bool ADD>
 int update_x(gk_ctx *c, double *x, int n_out) {
     ProfScope ps(c, GK_KID_UPDATE);
     cb_on(c) ? launch_update_x<ADD, float>(c, x, n_out) : launch_update_x<ADD, double>(c, x, n_out);
+    LAUNCHCHK();
+    return GK_OK;
+}
+
+// x += w: the last launch of the updates that do not end in update_x<true>
+int add_into(gk_ctx *c, double *x, const double *w) {
+    ProfScope ps(c, GK_KID_UPDATE);
+    gk::k_add<<<c->nblk_stream, gk::TPB, 0, c->st>>>(x, w, c->nloc);
     LAUNCHCHK();
     return GK_OK;
 }
@@ -458,311 +377,6 @@ int d2h_sync(gk_ctx *c, double *host, const double *dev, int count) {
     CHK(sync_st(c));
     if (c->prof) CHK(prof_harvest(c));
     std::memcpy(host, c->hcol_host, sizeof(double) * count);
-    return GK_OK;
-}
-
-// One temporal-blocked pass (gk_cheb.hip), tiles sized by the largest slab so
-// every rank writes the same number of partials (the all-reduced slab has one
-// length on all ranks).
-template <bool FIRST, bool LAST>
-int launch_cf(gk_ctx *c, int L, int acc, gk::CFArgs &a, i64 *np, bool sten = false) {
-    gk::CFLaunch q{};
-    q.L = L;
-    q.sten = sten;
-    q.first = FIRST;
-    q.last = LAST;
-    q.acc = acc;
-    q.lines = (c->nranks > 1 && c->max_lines > c->nlines) ? c->max_lines : c->nlines;
-    q.cus = c->res_cus > 0 ? c->res_cus : 256;
-    q.dev = c->dev;
-    q.st = c->st;
-    const int e = gk::cheb_launch(q, a, np);
-    if (e == gk::GK_CF_ESLOT) return set_err(GK_ERR_ARG, "Chebyshev pass grid exceeds a reduction slot");
-    if (e == gk::GK_CF_ESTEN) return set_err(GK_ERR_ARG, "fused-stencil Chebyshev pass outside its variants");
-    if (e == gk::GK_CF_ESPILL)
-        return set_err(GK_ERR_HIP, "Chebyshev pass (L = %d) was built with a register spill to scratch; refused", L);
-    if (e != 0) return set_err(GK_ERR_HIP, "Chebyshev pass launch: %s", hipGetErrorString((hipError_t)e));
-    return GK_OK;
-}
-
-// Chebyshev(k <= 16) as one or two temporal-blocked passes (gk_cheb.hip):
-// sweeps 1..min(k, 8) in the first, the rest in the second.  The input is `in`, or
-// with sten_v the vector whose stencil image stage 0 forms.
-int cheb_fused(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part,
-               const double *c1, const double *c2, double theta, const double *sten_v) {
-    ProfScope ps(c, GK_KID_PREC);
-    const int k = c->pdeg;
-    const int g1 = std::min(k, gk::CF_LMAX), g2 = k - g1;
-    const bool sten = sten_v != nullptr;  // one pass (k <= 8) taking v, stage 0 = the stencil
-    // On slabs every input of a pass brings L lines of each neighbour (deep halo).
-    const bool slabs = collective(c) && c->nranks > 1;
-    const bool has_lo = slabs && c->rank > 0, has_hi = slabs && c->rank < c->nranks - 1;
-    auto dlo = [&](int v) { return c->dh + (i64)(2 * v) * gk::CF_HMAX * c->N; };
-    auto dhi = [&](int v) { return c->dh + (i64)(2 * v + 1) * gk::CF_HMAX * c->N; };
-    auto deep = [&](gk::CFArgs &x, int v, const double *vec, int L) -> int {
-        if (slabs) CHK(halo_lines(c, vec, L, dlo(v), dhi(v)));
-        x.lo[v] = has_lo ? dlo(v) : nullptr;
-        x.hi[v] = has_hi ? dhi(v) : nullptr;
-        return GK_OK;
-    };
-    gk::CFArgs a{};
-    a.N = c->N;
-    a.nlines = c->nlines;
-    a.theta = theta;
-    a.din = sten ? sten_v : in;
-    a.vdot = vdot;
-    a.part = part;
-    CHK(deep(a, 0, a.din, g1 + (sten ? 1 : 0)));
-    for (int l = 0; l < g1; ++l) {
-        a.c1[l] = c1[l];
-        a.c2[l] = c2[l];
-    }
-    i64 np = 0;
-    if (g2 == 0) {
-        a.out = out;
-        CHK((launch_cf<true, true>(c, g1, acc, a, &np, sten)));
-        if (acc != gk::ACC_NONE) c->last_np = (int)np;
-        return GK_OK;
-    }
-    a.dout = c->dA;
-    a.rout = c->aux;
-    a.zout = c->dB;
-    CHK((launch_cf<true, false>(c, g1, gk::ACC_NONE, a, nullptr)));
-    gk::CFArgs b{};
-    b.N = c->N;
-    b.nlines = c->nlines;
-    b.din = c->dA;
-    b.rin = c->aux;
-    b.zin = c->dB;
-    CHK(deep(b, 0, c->dA, g2));
-    CHK(deep(b, 1, c->aux, g2));
-    CHK(deep(b, 2, c->dB, g2));
-    b.out = out;
-    b.vdot = vdot;
-    b.part = part;
-    for (int l = 0; l < g2; ++l) {
-        b.c1[l] = c1[g1 + l];
-        b.c2[l] = c2[g1 + l];
-    }
-    CHK((launch_cf<false, true>(c, g2, acc, b, &np)));
-    if (acc != gk::ACC_NONE) c->last_np = (int)np;
-    return GK_OK;
-}
-
-// The smallest slab of any rank, gathered once per communicator (collective:
-// every rank reaches it at the same point, the first Chebyshev application):
-// each rank contributes its nlines at its own position of a short vector that
-// is all-reduced by sum.  The decomposition may be any set of consecutive
-// slabs (gk_create / gk_comm_init take any line0, nlines), not only
-// slab_partition's.
-int ensure_min_lines(gk_ctx *c) {
-    if (c->min_lines > 0) return GK_OK;
-    if (!collective(c) || c->nranks == 1) {
-        c->min_lines = c->nlines;
-        return GK_OK;
-    }
-    std::vector<double> v(c->nranks, 0.0);
-    v[c->rank] = c->nlines;
-    double *d = slot(c, 3);
-    HIPCHK(hipMemcpyAsync(d, v.data(), sizeof(double) * c->nranks, hipMemcpyHostToDevice, c->st));
-    CHK(allreduce(c, d, c->nranks, true));
-    HIPCHK(hipMemcpyAsync(v.data(), d, sizeof(double) * c->nranks, hipMemcpyDeviceToHost, c->st));
-    CHK(sync_st(c));
-    int mn = c->nlines;
-    for (double x : v) mn = std::min(mn, (int)x);
-    c->min_lines = mn;
-    return GK_OK;
-}
-
-// Temporal-blocked Chebyshev passes: even N (two points per lane), k <= 16,
-// slabs below 2 GiB per vector, and on slabs every rank holding at least the
-// pass's L lines (the deep halo comes from the immediate neighbour only).  The
-// same answer on every rank.
-int cheb_fused_ok(gk_ctx *c, bool *ok) {
-    *ok = false;
-    if (!c->tune_cheb_fused || c->N % 2 != 0 || c->pdeg > 2 * gk::CF_LMAX) return GK_OK;
-    // the pass addresses slab vectors through 32-bit buffer offsets
-    if ((i64)c->N * std::max(c->nlines, c->max_lines) * 8 >= (1LL << 31)) return GK_OK;
-    if (!collective(c) || c->nranks == 1) {
-        *ok = true;
-        return GK_OK;
-    }
-    CHK(ensure_min_lines(c));
-    *ok = c->min_lines >= std::min(c->pdeg, gk::CF_LMAX);
-    return GK_OK;
-}
-
-// Chebyshev(k) coefficients of the sweeps (the per-sweep kernels' recurrence).
-int cheb_coefs(gk_ctx *c, double *c1, double *c2, double *theta) {
-    *theta = (c->p0 + c->p1) / 2.0;
-    const double delta = std::fabs(c->p1 - c->p0) / 2.0;
-    const double sigma = *theta / delta;
-    double rho0 = delta / *theta;
-    for (int it = 0; it < c->pdeg; ++it) {
-        const double rho1 = 1.0 / (2.0 * sigma - rho0);
-        c1[it] = rho1 * rho0;
-        c2[it] = 2.0 * rho1 / delta;
-        rho0 = rho1;
-    }
-    return GK_OK;
-}
-
-// out = M^-1 in (cbpr2 or Chebyshev sweeps); `in` is read in place (in != out, and
-// for Chebyshev neither is one of the sweeps' work vectors aux, dA, dB).
-int precond_sweeps(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part) {
-    bool fused = false;
-    if (c->pkind == GK_PREC_CHEB) CHK(cheb_fused_ok(c, &fused));
-    if (!fused) CHK(halo(c, in));  // the fused passes bring their own deep halos
-    if (c->pkind == GK_PREC_CBPR2) {
-        double d, alpha;
-        cbpr2_coefs(c, &d, &alpha);
-        gk::StArgs b2{};
-        b2.x = in;
-        b2.y = out;
-        b2.vdot = vdot;
-        b2.part = part;
-        b2.s1 = d;
-        b2.s2 = alpha;
-        return stencil(c, gk::OP_CBPR2, acc, b2);
-    }
-    // Chebyshev(k): k sweeps, each one stencil on d_k fused with the three
-    // vector updates (res, d, z); the first sweep builds d_0 = r/theta on load.
-    const double theta = (c->p0 + c->p1) / 2.0;
-    const double delta = std::fabs(c->p1 - c->p0) / 2.0;
-    const double sigma = theta / delta;
-    double rho0 = delta / theta;
-    if (fused) {
-        double c1[2 * gk::CF_LMAX], c2[2 * gk::CF_LMAX], th;
-        CHK(cheb_coefs(c, c1, c2, &th));
-        return cheb_fused(c, in, out, acc, vdot, part, c1, c2, th, nullptr);
-    }
-    double *dcur = c->dA, *dnext = c->dB;
-    for (int it = 0; it < c->pdeg; ++it) {
-        const double rho1 = 1.0 / (2.0 * sigma - rho0);
-        const double c1 = rho1 * rho0, c2 = 2.0 * rho1 / delta;
-        const bool last = (it == c->pdeg - 1);
-        gk::StArgs s{};
-        s.y = out;
-        s.s2 = c1;
-        s.s3 = c2;
-        s.vdot = vdot;
-        s.part = part;
-        if (it == 0) {
-            s.x = in;
-            s.s1 = theta;
-            s.o_res = last ? nullptr : c->aux;
-            s.o_d = last ? nullptr : dcur;
-            CHK(stencil(c, gk::OP_CHEB_FIRST, last ? acc : gk::ACC_NONE, s));
-        } else {
-            CHK(halo(c, dcur));
-            s.x = dcur;
-            s.in1 = c->aux;
-            s.in2 = out;
-            s.o_res = last ? nullptr : c->aux;
-            s.o_d = last ? nullptr : dnext;
-            CHK(stencil(c, gk::OP_CHEB_ITER, last ? acc : gk::ACC_NONE, s));
-            std::swap(dcur, dnext);
-        }
-        rho0 = rho1;
-    }
-    return GK_OK;
-}
-
-// The Arnoldi step's out = M^-1 (A v) with Chebyshev(k <= 8) as ONE pass whose
-// stage 0 forms z = A v itself: no stencil launch, no z vector (the pass reads
-// v; on slabs v brings k + 1 deep-halo lines).  *done = false: not applicable
-// (the caller takes the stencil + pass route).
-int op_precond_sten(gk_ctx *c, const double *v, double *out, int acc, const double *vdot, double *part,
-                    bool *done) {
-    *done = false;
-    if (c->pkind != GK_PREC_CHEB || acc != gk::ACC_DOT || !c->tune_cheb_sten || c->pdeg > gk::CF_LMAX ||
-        c->N < gk::CF_PTS)
-        return GK_OK;
-    bool fused = false;
-    CHK(cheb_fused_ok(c, &fused));
-    if (!fused || (collective(c) && c->nranks > 1 && c->min_lines < c->pdeg + 1)) return GK_OK;
-    double c1[2 * gk::CF_LMAX], c2[2 * gk::CF_LMAX], theta;
-    CHK(cheb_coefs(c, c1, c2, &theta));
-    CHK(cheb_fused(c, nullptr, out, acc, vdot, part, c1, c2, theta, v));
-    *done = true;
-    return GK_OK;
-}
-
-// out = M^-1 (A v)  or  out = M^-1 (b - A v) (resid); the LAST sweep carries
-// the fused reduction `acc` (dot with vdot, or norm) into slab `part`.
-// Reference: gmres_mgsr.f90:336-337 (step), :314-320 (cycle start).
-int op_precond(gk_ctx *c, const double *v, double *out, bool resid, int acc, const double *vdot,
-               double *part) {
-    if (!resid) {
-        bool done = false;
-        CHK(op_precond_sten(c, v, out, acc, vdot, part, &done));
-        if (done) return GK_OK;
-    }
-    CHK(halo(c, v));
-    gk::StArgs a{};
-    if (c->pkind == GK_PREC_IDENTITY) {
-        a.x = v;
-        a.in1 = c->b;
-        a.y = out;
-        a.vdot = vdot;
-        a.part = part;
-        return stencil(c, resid ? gk::OP_RESID : gk::OP_PLAIN, acc, a);
-    }
-    // z = A v   (or b - A v)
-    a.x = v;
-    a.in1 = c->b;
-    a.y = c->z;
-    CHK(stencil(c, resid ? gk::OP_RESID : gk::OP_PLAIN, gk::ACC_NONE, a));
-    return precond_sweeps(c, c->z, out, acc, vdot, part);
-}
-
-// out = b - A x, fused with its norm: the cycle start of right preconditioning (and
-// of the identity preconditioner).  np_st partials in `part`.
-int resid_norm(gk_ctx *c, double *out, double *part) {
-    CHK(halo(c, c->x));
-    gk::StArgs a{};
-    a.x = c->x;
-    a.in1 = c->b;
-    a.y = out;
-    a.part = part;
-    return stencil(c, gk::OP_RESID, gk::ACC_NORM, a);
-}
-
-// out = A (M^-1 v), the right-preconditioned Arnoldi operator (M not the identity),
-// with the fused reduction `acc` (none, or the dot with vdot) on the launch that
-// writes out.  One launch where k_right_cbpr2 applies; else z = M^-1 v by the
-// preconditioner's own route (N ranks: halo of v, the sweeps, halo of z) and the
-// plain stencil.
-int op_right(gk_ctx *c, const double *v, double *out, int acc, const double *vdot, double *part) {
-    if (right_fused_ok(c)) return right_cbpr2(c, v, out, acc, vdot, part);
-    CHK(precond_sweeps(c, v, c->z, gk::ACC_NONE, nullptr, nullptr));
-    CHK(halo(c, c->z));
-    gk::StArgs a{};
-    a.x = c->z;
-    a.y = out;
-    a.vdot = vdot;
-    a.part = part;
-    return stencil(c, gk::OP_PLAIN, acc, a);
-}
-
-// x += M^-1 t, the cycle-end update of a right-preconditioned Householder cycle (M not
-// the identity; t is not z).  Where k_right_cbpr2 applies, ONE march: the cbpr2 sweep
-// with the accumulating output (OP_CBPR2_ADD: t and x read, x written, z never stored).
-// Else z = M^-1 t by the preconditioner's own route and k_add -- the same expressions
-// in the same order, so x is bit-identical on both routes.
-int add_precond(gk_ctx *c, const double *t) {
-    if (right_fused_ok(c)) {
-        gk::StArgs a{};
-        a.x = t;
-        a.in1 = c->x;
-        a.y = c->x;
-        cbpr2_coefs(c, &a.s1, &a.s2);
-        return stencil(c, gk::OP_CBPR2_ADD, gk::ACC_NONE, a);
-    }
-    CHK(precond_sweeps(c, t, c->z, gk::ACC_NONE, nullptr, nullptr));
-    ProfScope ps(c, GK_KID_UPDATE);
-    gk::k_add<<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->x, c->z, c->nloc);
-    LAUNCHCHK();
     return GK_OK;
 }
 
@@ -1265,11 +879,7 @@ int gk_set_rhs_ones(gk_ctx *c) {
     HIPCHK(hipSetDevice(c->dev));
     gk::k_fill<<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->aux, 1.0, c->nloc);
     LAUNCHCHK();
-    CHK(halo(c, c->aux));
-    gk::StArgs a{};
-    a.x = c->aux;
-    a.y = c->b;
-    CHK(stencil(c, gk::OP_PLAIN, gk::ACC_NONE, a));
+    CHK(op_A(c, c->aux, c->b, gk::ACC_NONE, nullptr, nullptr));
     CHK(sync_st(c));
     c->beta0 = -1.0;
     return GK_OK;
@@ -1367,13 +977,7 @@ int gk_true_residual(gk_ctx *c, double *rel) {
     HIPCHK(hipSetDevice(c->dev));
     double b0;
     if (c->beta0 < 0) CHK(gk_rhs_norm(c, &b0));
-    CHK(halo(c, c->x));
-    gk::StArgs a{};
-    a.x = c->x;
-    a.in1 = c->b;
-    a.y = c->aux;
-    a.part = slot(c, 2);
-    CHK(stencil(c, gk::OP_RESID, gk::ACC_NORM, a));
+    CHK(op_resid(c, c->x, c->aux, gk::ACC_NORM, slot(c, 2)));
     CHK(allreduce(c, slot(c, 2), c->np_st));
     CHK(finalize(c, slot(c, 2), c->np_st, c->scal + 1, 1));
     double r;
@@ -1397,7 +1001,7 @@ int gk_mgs_cycle_start(gk_ctx *c, double *beta) {
         graph_reset(c);
     }
     if (right_prec(c))  // w = b - A x: the Arnoldi residual is the true residual
-        CHK(resid_norm(c, c->w, slot(c, 0)));
+        CHK(op_resid(c, c->x, c->w, gk::ACC_NORM, slot(c, 0)));
     else
         CHK(op_precond(c, c->x, c->w, true, gk::ACC_NORM, nullptr, slot(c, 0)));
     CHK(allreduce(c, slot(c, 0), c->last_np));
@@ -1516,10 +1120,7 @@ int gk_update_x(gk_ctx *c, const double *y, int n_out) {
     HIPCHK(hipMemcpyAsync(c->ydev, y, sizeof(double) * n_out, hipMemcpyHostToDevice, c->st));
     if (right_prec(c)) {  // x += M^-1 (V y): t = V y in w, M^-1 t in z
         CHK(update_x<false>(c, c->w, n_out));
-        CHK(precond_sweeps(c, c->w, c->z, gk::ACC_NONE, nullptr, nullptr));
-        ProfScope ps(c, GK_KID_UPDATE);
-        gk::k_add<<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->x, c->z, c->nloc);
-        LAUNCHCHK();
+        CHK(add_precond_sweeps(c, c->w));
     } else {
         CHK(update_x<true>(c, c->x, n_out));
     }
@@ -1572,15 +1173,12 @@ static int hh_prec_arg(const gk_ctx *c, int precondition) {
     return GK_OK;
 }
 
-static int hh_pivot(gk_ctx *c, int j, double *hostout, int nout) {
+static int hh_pivot(gk_ctx *c, int j) {
     // hb[0..j] = w(1:j+1) from the owning rank, broadcast
     const int root = owner_of(c, j);
     if (c->rank == root)
         HIPCHK(hipMemcpyAsync(c->hb, c->w + (0 - c->g0), sizeof(double) * (j + 1), hipMemcpyDeviceToDevice, c->st));
-    CHK(bcast(c, c->hb, j + 1, root));
-    return GK_OK;
-    (void)hostout;
-    (void)nout;
+    return bcast(c, c->hb, j + 1, root);
 }
 
 int gk_hh_cycle_start(gk_ctx *c, int precondition, double *g1) {
@@ -1591,23 +1189,16 @@ int gk_hh_cycle_start(gk_ctx *c, int precondition, double *g1) {
     if (c->nranks > 1 && c->rank == 0 && c->nloc < c->m + 2)
         return set_err(GK_ERR_ARG, "Householder path needs the first slab to hold m+2 unknowns");
     CHK(hh_prec_arg(c, precondition));
-    if (precondition == GK_HH_PREC_LEFT) {
+    if (precondition == GK_HH_PREC_LEFT)
         CHK(op_precond(c, c->x, c->w, true, gk::ACC_NORM, nullptr, slot(c, 0)));
-    } else {  // none, or right: the Arnoldi residual is the true residual b - A x
-        CHK(halo(c, c->x));
-        gk::StArgs a{};
-        a.x = c->x;
-        a.in1 = c->b;
-        a.y = c->w;
-        a.part = slot(c, 0);
-        CHK(stencil(c, gk::OP_RESID, gk::ACC_NORM, a));
-    }
+    else  // none, or right: the Arnoldi residual is the true residual b - A x
+        CHK(op_resid(c, c->x, c->w, gk::ACC_NORM, slot(c, 0)));
     CHK(allreduce(c, slot(c, 0), c->last_np));
     // GK_TUNE_HH_NORM_ORDER: beta = norm2(w) and norm2 of the fixed w in the reference's
     // order (gmres_hh.f90:250-253), one rank
     const bool seq = hh_seq_norms(c);
     if (seq) CHK(norm2_seq(c, c->w, c->nloc, slot(c, 0)));
-    CHK(hh_pivot(c, 0, nullptr, 0));
+    CHK(hh_pivot(c, 0));
     {
         ProfScope ps(c, GK_KID_OTHER);
         gk::k_hh_pivot<<<1, gk::TPB, 0, c->st>>>(c->hb, slot(c, 0), seq ? 1 : c->last_np, 0, c->hcol, c->scal + 2,
@@ -1664,13 +1255,7 @@ int gk_hh_step_async(gk_ctx *c, int j, int precondition) {
     } else if (precondition == GK_HH_PREC_RIGHT && c->pkind != GK_PREC_IDENTITY) {
         CHK(op_right(c, c->vj, c->w, gk::ACC_DOT, P, slot(c, s0)));
     } else {
-        CHK(halo(c, c->vj));
-        gk::StArgs a{};
-        a.x = c->vj;
-        a.y = c->w;
-        a.vdot = P;
-        a.part = slot(c, s0);
-        CHK(stencil(c, gk::OP_PLAIN, gk::ACC_DOT, a));
+        CHK(op_A(c, c->vj, c->w, gk::ACC_DOT, P, slot(c, s0)));
     }
     int np = c->last_np;
     // N ranks on the device exchange: <w, P_1> summed across ranks inside the launch (GK_TUNE_RES_FOLD)
@@ -1718,7 +1303,7 @@ int gk_hh_step_async(gk_ctx *c, int j, int precondition) {
         CHK(norm2_seq(c, c->w + j, c->nloc - j, slot(c, s0)));
         np = 1;
     }
-    CHK(hh_pivot(c, j, nullptr, 0));
+    CHK(hh_pivot(c, j));
     {
         ProfScope ps(c, GK_KID_OTHER);
         const int m2 = c->m + 2;
@@ -1762,9 +1347,7 @@ int gk_hh_update_x(gk_ctx *c, const double *y, int n_out) {
     if (c->hh_prec == GK_HH_PREC_RIGHT && c->pkind != GK_PREC_IDENTITY) {  // x += M^-1 t, t in w
         CHK(add_precond(c, c->w));
     } else {
-        ProfScope ps(c, GK_KID_UPDATE);
-        gk::k_add<<<c->nblk_stream, gk::TPB, 0, c->st>>>(c->x, c->w, c->nloc);
-        LAUNCHCHK();
+        CHK(add_into(c, c->x, c->w));
     }
     CHK(sync_st(c));
     if (c->prof) CHK(prof_harvest(c));
@@ -1818,18 +1401,10 @@ int gk_apply(gk_ctx *c, int what, const double *in, double *out) {
     c->cycle_mgs = c->cycle_hh = false;  // clobbers the work vectors
     if (what == 0) {
         HIPCHK(hipMemcpyAsync(c->vj, in, sizeof(double) * c->nloc, hipMemcpyHostToDevice, c->st));
-        CHK(halo(c, c->vj));
-        gk::StArgs a{};
-        a.x = c->vj;
-        a.y = c->w;
-        CHK(stencil(c, gk::OP_PLAIN, gk::ACC_NONE, a));
+        CHK(op_A(c, c->vj, c->w, gk::ACC_NONE, nullptr, nullptr));
     } else {
         HIPCHK(hipMemcpyAsync(c->z, in, sizeof(double) * c->nloc, hipMemcpyHostToDevice, c->st));
-        if (c->pkind == GK_PREC_IDENTITY) {
-            HIPCHK(hipMemcpyAsync(c->w, c->z, sizeof(double) * c->nloc, hipMemcpyDeviceToDevice, c->st));
-        } else {
-            CHK(precond_sweeps(c, c->z, c->w, gk::ACC_NONE, nullptr, nullptr));
-        }
+        CHK(op_Minv_or_copy(c, c->z, c->w));
     }
     HIPCHK(hipMemcpyAsync(out, c->w, sizeof(double) * c->nloc, hipMemcpyDeviceToHost, c->st));
     CHK(sync_st(c));
@@ -2154,16 +1729,7 @@ int gk_poisson5(int nside, int nlines, const double *x, const double *hlo, const
         return set_err(GK_ERR_ARG, "device pointers must be 16-byte aligned");
     gk_ctx c;
     CHK(stateless_ctx(c, nside, nlines, (i64)nside * nlines, stream));
-    gk::StArgs a{};
-    a.x = x;
-    a.y = y;
-    a.N = nside;
-    a.nlines = nlines;
-    a.JT = c.JT;
-    a.hlo = hlo;
-    a.hhi = hhi;
-    int rc = (c.vec == 2) ? launch_stencil_v<2, gk::OP_PLAIN, gk::ACC_NONE>(&c, a)
-                          : launch_stencil_v<1, gk::OP_PLAIN, gk::ACC_NONE>(&c, a);
+    const int rc = stencil_plain_raw(&c, x, hlo, hhi, y);
     release_stateless(c);
     return rc;
 }
@@ -2177,24 +1743,17 @@ int gk_precond_apply(int nside, int kind, const double *params, int degree, cons
     gk_ctx c;
     CHK(stateless_ctx(c, nside, nside, n, stream));
     int rc = gk_set_precond(&c, kind, params, params ? 2 : 0, degree);
-    if (rc == GK_OK && kind == GK_PREC_IDENTITY) {
-        rc = hipMemcpyAsync(z, r, sizeof(double) * n, hipMemcpyDeviceToDevice, c.st) == hipSuccess
-                 ? GK_OK
-                 : set_err(GK_ERR_HIP, "copy failed");
-    } else if (rc == GK_OK) {
-        if (scratch == nullptr && kind == GK_PREC_CHEB) {
-            rc = set_err(GK_ERR_ARG, "Chebyshev needs 3 scratch vectors");
-        } else {
-            // op_precond expects z = A v already formed for a step; here the input
-            // IS the residual, so run the preconditioner sweeps directly on r.
-            c.z = const_cast<double *>(r);
-            c.aux = scratch;
-            c.dA = scratch ? scratch + n : nullptr;
-            c.dB = scratch ? scratch + 2 * n : nullptr;
-            rc = precond_sweeps(&c, c.z, z, gk::ACC_NONE, nullptr, nullptr);
-        }
+    if (rc == GK_OK && scratch == nullptr && kind == GK_PREC_CHEB)
+        rc = set_err(GK_ERR_ARG, "Chebyshev needs 3 scratch vectors");
+    if (rc == GK_OK) {
+        // op_precond expects z = A v already formed for a step; here the input
+        // IS the residual, so run the preconditioner sweeps directly on r.
+        c.aux = scratch;
+        c.dA = scratch ? scratch + n : nullptr;
+        c.dB = scratch ? scratch + 2 * n : nullptr;
+        rc = op_Minv_or_copy(&c, r, z);
     }
-    c.z = c.aux = c.dA = c.dB = nullptr;
+    c.aux = c.dA = c.dB = nullptr;
     release_stateless(c);
     return rc;
 }
@@ -2283,11 +1842,7 @@ extern "C" int gk_lanczos_bounds(gk_ctx *c, int k, double *lmin, double *lmax) {
     std::vector<double> al, be;
     double beta = 0.0;
     for (int it = 0; it < k; ++it) {
-        CHK(halo(c, q));
-        gk::StArgs a{};
-        a.x = q;
-        a.y = w;
-        CHK(stencil(c, gk::OP_PLAIN, gk::ACC_NONE, a));   // w = A q
+        CHK(op_A(c, q, w, gk::ACC_NONE, nullptr, nullptr));  // w = A q
         if (beta != 0.0) CHK(axpy_host(c, w, -beta, qprev));
         double alpha;
         CHK(dot_host(c, w, q, &alpha));
@@ -2340,19 +1895,14 @@ int gk_vec_apply(gk_ctx *c, int what, int in, int out) {
     c->cycle_mgs = c->cycle_hh = false;
     if (what == 2 && c->pkind != GK_PREC_IDENTITY)  // out = A M^-1 in, the right-preconditioned step's operator
         return op_right(c, vi, vo, gk::ACC_NONE, nullptr, nullptr);
-    if (what != 1) {  // A in (what = 2 with the identity preconditioner is A itself)
-        CHK(halo(c, vi));
-        gk::StArgs a{};
-        a.x = vi;
-        a.y = vo;
-        return stencil(c, gk::OP_PLAIN, gk::ACC_NONE, a);
+    if (what != 1)  // A in (what = 2 with the identity preconditioner is A itself)
+        return op_A(c, vi, vo, gk::ACC_NONE, nullptr, nullptr);
+    const double *src = vi;
+    if (c->pkind != GK_PREC_IDENTITY) {  // the sweeps read their input from z
+        HIPCHK(hipMemcpyAsync(c->z, vi, sizeof(double) * c->nloc, hipMemcpyDeviceToDevice, c->st));
+        src = c->z;
     }
-    if (c->pkind == GK_PREC_IDENTITY) {
-        HIPCHK(hipMemcpyAsync(vo, vi, sizeof(double) * c->nloc, hipMemcpyDeviceToDevice, c->st));
-        return GK_OK;
-    }
-    HIPCHK(hipMemcpyAsync(c->z, vi, sizeof(double) * c->nloc, hipMemcpyDeviceToDevice, c->st));
-    return precond_sweeps(c, c->z, vo, gk::ACC_NONE, nullptr, nullptr);
+    return op_Minv_or_copy(c, src, vo);
 }
 
 int gk_vec_dot(gk_ctx *c, int a, int b, double *result) {

@@ -1,5 +1,5 @@
 // gk_host.hpp -- internal header of the host-side units of libgmres_hip.so
-// (gk_api.hip, gk_comm.hip, gk_sr_api.hip); never installed.  The context, the
+// (gk_api.hip, gk_op.hip, gk_comm.hip, gk_sr_api.hip); never installed.  The context, the
 // error / check macros, the profiling scope and the few helpers that cross units.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -201,7 +201,7 @@ int prof_harvest(gk_ctx *c);
 void graph_reset(gk_ctx *c);
 void set_geometry(gk_ctx *c);
 int check_ctx(gk_ctx *c);
-int precond_sweeps(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part);
+int add_into(gk_ctx *c, double *x, const double *w);  // x += w (k_add, GK_KID_UPDATE)
 int fill_hash(gk_ctx *c, double *x, unsigned long long seed);  // k_fill_hash of the global index
 // The short-recurrence solvers keep their vectors in the Krylov columns and their
 // state on the device: any call that changes the operator data, the right-hand
@@ -222,6 +222,19 @@ template <class T>  // column k (0-based) of the MGS-R basis in the type T it is
 inline T *vcol(const gk_ctx *c, int k) { return reinterpret_cast<T *>(c->V) + (i64)k * c->ld; }
 inline double *cb_v1w(const gk_ctx *c) { return c->V + (i64)(c->m - 1) * c->ld; }
 inline double *cb_vjw(const gk_ctx *c) { return c->V + (i64)c->m * c->ld; }
+
+// gk_op.hip -- the operator A, the preconditioner M and their products.  acc: the reduction
+// fused into the launch that writes `out` (gk::ACC_*; ACC_DOT with vdot), its partials in
+// `part`, their count in c->last_np.  Every one exchanges the halos of what it reads.
+int op_A(gk_ctx *c, const double *v, double *out, int acc, const double *vdot, double *part);
+int op_resid(gk_ctx *c, const double *x, double *out, int acc, double *part);  // out = b - A x
+int stencil_plain_raw(gk_ctx *c, const double *x, const double *hlo, const double *hhi, double *y);
+int precond_sweeps(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part);
+int op_Minv_or_copy(gk_ctx *c, const double *in, double *out);
+int op_precond(gk_ctx *c, const double *v, double *out, bool resid, int acc, const double *vdot, double *part);
+int op_right(gk_ctx *c, const double *v, double *out, int acc, const double *vdot, double *part);
+int add_precond(gk_ctx *c, const double *t);         // x += M^-1 t, one march where cbpr2 allows
+int add_precond_sweeps(gk_ctx *c, const double *t);  // ... always the sweeps into z, then add_into
 
 // gk_comm.hip
 bool collective(const gk_ctx *c);

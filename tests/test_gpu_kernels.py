@@ -78,6 +78,27 @@ def test_precond_bitexact(oracle, N, kind, degree):
     assert np.array_equal(zd.cpu().numpy(), ref)
 
 
+@pytest.mark.parametrize("N", [2, 65, 514])
+@pytest.mark.parametrize("kind,degree", [("identity", 1), ("cbpr2", 1), ("cheb", 4)])
+def test_context_apply_bitexact(oracle, N, kind, degree):
+    """A v and M^-1 v of a context, from the host (gk_apply) and on its resident vectors
+    (gk_vec_apply), the identity's copy included.  N = 2 is the smallest grid; 65 is odd
+    (one point per lane, Chebyshev by the per-sweep kernels); 514 puts two points in a
+    second workgroup along i."""
+    import gmres_amd as ga
+
+    v = np.random.default_rng(N + degree).standard_normal(N * N)
+    kid = {"cbpr2": oracle.PREC_CBPR2, "cheb": oracle.PREC_CHEB, "identity": oracle.PREC_IDENTITY}[kind]
+    refs = [oracle.stvec(v, N), oracle.precond(kid, v, N, params=(8.2, 0.2), degree=degree)]
+    with ga.Context(N, 4) as c:
+        c.set_precond(kind, (8.2, 0.2), degree)
+        for what in (0, 1):
+            assert np.array_equal(c.apply(v, what), refs[what])
+            c.set_x(v)
+            c.vec_apply(what, 0, 2)  # x -> V(:,1)
+            assert np.array_equal(_ctx_col(c, 0), refs[what])
+
+
 @pytest.mark.parametrize("n", [1, 2, 3, 1000, 4097, 1 << 20, (1 << 20) + 3])
 def test_dot_and_project(n):
     import gmres_amd.solver as S
