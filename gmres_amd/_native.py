@@ -45,6 +45,7 @@ GK_TUNE_RES_PF = 27
 GK_TUNE_RES_PIPE = 30
 GK_TUNE_RIGHT_FUSED = 31
 GK_TUNE_RES_PIPE_CARRY = 32
+GK_TUNE_MG_FUSED = 33
 GK_SIDE_LEFT, GK_SIDE_RIGHT = 0, 1
 GK_BASIS_F64, GK_BASIS_F32 = 0, 1
 GK_ORTH_MGSR, GK_ORTH_CGS2 = 0, 1
@@ -52,6 +53,8 @@ GK_CGS_KB = 8  # columns a dots workgroup of the CGS2 step batches (GK_CGS_KB=16
 GK_HH_PREC_NONE, GK_HH_PREC_LEFT, GK_HH_PREC_RIGHT = 0, 1, 2
 GK_ERR_ARG, GK_ERR_STATE = -1, -4
 GK_PREC_IDENTITY, GK_PREC_CBPR2, GK_PREC_CHEB = 0, 1, 2
+GK_PREC_MG = 3  # aggregation multigrid V-cycle (gk_mg_plan_query / gk_mg_info: GK_MG_INFO_LEN ints)
+GK_MG_INFO_LEN = 35
 (GK_KID_PROJ, GK_KID_STENCIL, GK_KID_SCALE, GK_KID_UPDATE, GK_KID_COMM, GK_KID_OTHER, GK_KID_RES, GK_KID_PREC,
  GK_KID_HALO, GK_KID_GRAPH) = range(10)
 # short-recurrence passes (GK_KID_SR + pass kind, gmres_amd/csrc/gk_sr.hpp)
@@ -110,6 +113,9 @@ _SIGS = {
     "gk_xchg_enable": (c_int, [c_vp, c_int]),
     "gk_xchg_selftest": (c_int, [c_vp, c_int]),
     "gk_set_precond": (c_int, [c_vp, c_int, _dp, c_int, c_int]),
+    "gk_mg_plan_query": (c_int, [c_int, _ip]),
+    "gk_mg_info": (c_int, [c_vp, _ip]),
+    "gk_mg_transfer": (c_int, [c_vp, c_int, c_int, _dp, _dp, _dp]),
     "gk_set_precond_side": (c_int, [c_vp, c_int]),
     "gk_set_basis_precision": (c_int, [c_vp, c_int]),
     "gk_get_basis_precision": (c_int, [c_vp, _ip]),

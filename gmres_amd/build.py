@@ -53,10 +53,13 @@ HIP_UNITS = ([_unit("gk_api"), _unit("gk_op")]
 HIP_UNITS_CB = [_unit("gk_cb")]
 # ... and the unit of the opt-in CGS2 Arnoldi step (batched dots, reduce, j-column AXPY): twelve in all
 HIP_UNITS_CGS = [_unit("gk_cgs")]
-HIP_SOURCES = sorted({u[0] for u in HIP_UNITS + HIP_UNITS_CB + HIP_UNITS_CGS})
+# ... and the unit of the multigrid preconditioner's transfer and closing kernels: thirteen with it
+HIP_UNITS_MG = [_unit("gk_mg")]
+HIP_UNITS_ALL = HIP_UNITS + HIP_UNITS_CB + HIP_UNITS_CGS + HIP_UNITS_MG
+HIP_SOURCES = sorted({u[0] for u in HIP_UNITS_ALL})
 HIP_HEADERS = [os.path.join(CSRC, h) for h in ("gk_common.hpp", "gk_kernels.hpp", "gk_stencil.hpp", "gk_cheb.hpp", "gk_res.hpp",
                                                 "gk_blk.hpp", "gk_sr.hpp", "gk_host.hpp", "gk_resident.hpp",
-                                                "gk_cb.hpp", "gk_cgs.hpp")]
+                                                "gk_cb.hpp", "gk_cgs.hpp", "gk_mg.hpp")]
 HIP_DEPS = HIP_SOURCES + HIP_HEADERS + [os.path.join(ROOT, "include", "gmres_hip.h")]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall"]
 F_SOURCES = [os.path.join(FSRC, "gmres_hip.f90")]
@@ -110,7 +113,7 @@ def _compile_link(so: str, defines: list[str]) -> None:
     pass at run time; a spilled resident kernel holds w in scratch memory): the
     build fails here, naming them."""
     objs, procs = [], []
-    for src, unit_defs, oname in HIP_UNITS + HIP_UNITS_CB + HIP_UNITS_CGS:
+    for src, unit_defs, oname in HIP_UNITS_ALL:
         obj = os.path.join(os.path.dirname(so), oname)
         cmd = [hipcc(), *HIP_FLAGS, *[f"-D{x}" for x in defines + unit_defs], "-c", src, "-o", obj,
                "-Rpass-analysis=kernel-resource-usage"]
@@ -122,7 +125,7 @@ def _compile_link(so: str, defines: list[str]) -> None:
         err = p.communicate()[1]
         sys.stderr.write("".join(l + "\n" for l in err.splitlines() if "warning:" in l or "error" in l))
         for name in ("k_cheb_fused", "k_mgs_wpc", "k_mgs_wres", "k_mgs_res", "k_mgs_blk", "k_right_cbpr2",
-                     "k_mgs_wcb", "k_stencil", "k_cgs_"):
+                     "k_mgs_wcb", "k_stencil", "k_cgs_", "k_mg_"):
             bad += _scratch_kernels(err, name)
     if any(p.returncode for p in procs):
         raise subprocess.CalledProcessError(max(p.returncode for p in procs), "hipcc")

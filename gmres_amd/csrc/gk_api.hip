@@ -26,6 +26,7 @@
 #include "gk_cgs.hpp"
 #include "gk_host.hpp"
 #include "gk_kernels.hpp"
+#include "gk_mg.hpp"
 #include "gk_resident.hpp"
 
 using namespace gkh;
@@ -739,6 +740,7 @@ int gk_destroy(gk_ctx *c) {
     }
     if (c->st) (void)hipStreamSynchronize(c->st);
     graph_reset(c);
+    mg_free(c);
     if (c->comm) ncclCommDestroy(c->comm);
     if (c->lev_a) (void)hipEventDestroy(c->lev_a);
     if (c->lev_b) (void)hipEventDestroy(c->lev_b);
@@ -786,10 +788,28 @@ int gk_local_size(gk_ctx *c, long long *nloc) {
 int gk_set_precond(gk_ctx *c, int kind, const double *params, int nparams, int degree) {
     CHK(check_ctx(c));
     sr_invalidate(c);
-    if (kind < GK_PREC_IDENTITY || kind > GK_PREC_CHEB) return set_err(GK_ERR_ARG, "bad precond kind %d", kind);
+    if (kind < GK_PREC_IDENTITY || kind > GK_PREC_MG) return set_err(GK_ERR_ARG, "bad precond kind %d", kind);
     if (kind != GK_PREC_IDENTITY && (params == nullptr || nparams < 2))
         return set_err(GK_ERR_ARG, "precond needs params(1:2)");
     if (kind == GK_PREC_CHEB && (degree < 1 || degree > 64)) return set_err(GK_ERR_ARG, "bad degree %d", degree);
+    if (kind == GK_PREC_MG) {  // everything checked, and the hierarchy built, before the context changes
+        int sides[gk::MG_LMAX];
+        if (gk::mg_levels(c->N, sides) < 2)
+            return set_err(GK_ERR_ARG, "multigrid needs an even N with N / 2 >= %d (N = %d)", gk::MG_NMIN, c->N);
+        if (degree < 1 || degree > gk::MG_DEG_MAX)
+            return set_err(GK_ERR_ARG, "multigrid smoother degree %d outside 1..%d", degree, gk::MG_DEG_MAX);
+        if (std::fabs(params[1] - params[0]) == 0.0) return set_err(GK_ERR_ARG, "multigrid smoother interval is empty");
+        if (c->nranks > 1 || c->comm != nullptr || c->lg != nullptr || c->xs_on || c->line0 != 0 || c->nlines != c->N)
+            return set_err(GK_ERR_STATE, "multigrid needs the whole grid on one rank (no communicator)");
+        if (c->V == nullptr) return set_err(GK_ERR_ARG, "multigrid needs a context (gk_create)");
+        HIPCHK(hipSetDevice(c->dev));
+        // the same cycle again (the host-array plug-in sets it per application): keep the hierarchy
+        const bool same = c->pkind == GK_PREC_MG && c->mg.size() >= 2 && c->p0 == params[0] && c->p1 == params[1] &&
+                          c->pdeg == degree;
+        if (!same) CHK(mg_build(c, params[0], params[1], degree));
+    } else {
+        mg_free(c);
+    }
     c->pkind = kind;
     if (params != nullptr && nparams >= 2) {
         c->p0 = params[0];
@@ -1466,6 +1486,7 @@ int gk_set_tuning(gk_ctx *c, int key, int value) {
             break;
         case GK_TUNE_VERR_ORDER: c->tune_verr_order = value != 0; break;
         case GK_TUNE_RIGHT_FUSED: c->tune_right_fused = value != 0; break;
+        case GK_TUNE_MG_FUSED: c->tune_mg_fused = value != 0; break;
         case GK_TUNE_RES_TIMEOUT_MS:
             if (value < 1) return set_err(GK_ERR_ARG, "timeout must be >= 1 ms");
             c->res_timeout_ms = value;
@@ -1647,6 +1668,50 @@ int gk_res_plan_query(long long nloc, int cus, int share, int hh, int nt, int bl
     return GK_OK;
 }
 
+// info: [0] levels, [1] the coarsest level's sweep count, [2] the smoother degree (0 from the
+// plan query), [3 ..] the level sides
+static void mg_info_fill(const int *sides, int nl, int cdeg, int deg, int *info) {
+    for (int k = 0; k < GK_MG_INFO_LEN; ++k) info[k] = 0;
+    info[0] = nl;
+    info[1] = cdeg;
+    info[2] = deg;
+    for (int l = 0; l < nl && 3 + l < GK_MG_INFO_LEN; ++l) info[3 + l] = sides[l];
+}
+
+int gk_mg_plan_query(int nside, int *info) {
+    static_assert(GK_MG_INFO_LEN >= 3 + gk::MG_LMAX, "gk_mg_plan_query layout");
+    if (info == nullptr) return set_err(GK_ERR_ARG, "null info");
+    int sides[gk::MG_LMAX];
+    const int nl = gk::mg_levels(nside, sides);
+    if (nl < 2) return set_err(GK_ERR_ARG, "multigrid needs an even N with N / 2 >= %d (N = %d)", gk::MG_NMIN, nside);
+    double lo, hi;
+    mg_info_fill(sides, nl, gk::mg_coarse_degree(sides[nl - 1], &lo, &hi), 0, info);
+    return GK_OK;
+}
+
+int gk_mg_info(gk_ctx *c, int *info) {
+    CHK(check_ctx(c));
+    if (info == nullptr) return set_err(GK_ERR_ARG, "null info");
+    if (c->pkind != GK_PREC_MG || c->mg.size() < 2) return set_err(GK_ERR_STATE, "no multigrid preconditioner set");
+    int sides[gk::MG_LMAX];
+    const int nl = (int)c->mg.size();
+    for (int l = 0; l < nl; ++l) sides[l] = c->mg[l].lc->N;
+    mg_info_fill(sides, nl, c->mg_cdeg, c->pdeg, info);
+    return GK_OK;
+}
+
+int gk_mg_transfer(gk_ctx *c, int what, int level, const double *a, const double *b, double *out) {
+    CHK(check_ctx(c));
+    if (c->pkind != GK_PREC_MG || c->mg.size() < 2) return set_err(GK_ERR_STATE, "no multigrid preconditioner set");
+    if (what < 0 || what > 2 || level < 0 || level + 1 >= (int)c->mg.size() || a == nullptr || out == nullptr ||
+        (what != 0 && b == nullptr))
+        return set_err(GK_ERR_ARG, "bad gk_mg_transfer(%d, level %d)", what, level);
+    HIPCHK(hipSetDevice(c->dev));
+    c->cycle_mgs = c->cycle_hh = false;  // clobbers the hierarchy's work vectors
+    sr_invalidate(c);
+    return mg_transfer(c, what, level, a, b, out);
+}
+
 int gk_res_info(gk_ctx *c, int hh, long long *info) {
     CHK(check_ctx(c));
     if (info == nullptr) return set_err(GK_ERR_ARG, "null info");
@@ -1737,6 +1802,7 @@ int gk_poisson5(int nside, int nlines, const double *x, const double *hlo, const
 int gk_precond_apply(int nside, int kind, const double *params, int degree, const double *r, double *z,
                      double *scratch, void *stream) {
     if (nside < 2 || r == nullptr || z == nullptr) return set_err(GK_ERR_ARG, "bad precond args");
+    if (kind == GK_PREC_MG) return set_err(GK_ERR_ARG, "multigrid needs a context: gk_set_precond(ctx, GK_PREC_MG, ...)");
     if (!aligned16(r) || !aligned16(z) || !aligned16(scratch))
         return set_err(GK_ERR_ARG, "device pointers must be 16-byte aligned");
     const i64 n = (i64)nside * nside;

@@ -472,6 +472,7 @@ int gk_comm_init(gk_ctx *c, int nranks, int rank, int max_lines, const unsigned 
     if (c == nullptr || nranks < 1 || rank < 0 || rank >= nranks || max_lines < c->nlines)
         return set_err(GK_ERR_ARG, "bad comm args");
     if (cb_on(c)) return set_err(GK_ERR_STATE, "the FP32 basis needs a single-rank context (gk_set_basis_precision)");
+    if (c->pkind == GK_PREC_MG) return set_err(GK_ERR_STATE, "the multigrid preconditioner needs a single-rank context");
     graph_reset(c);
     HIPCHK(hipSetDevice(c->dev));
     c->nranks = nranks;
@@ -512,6 +513,7 @@ int gk_comm_init_local(gk_ctx *c, gk_group *g, int rank, int max_lines) {
     if (c == nullptr || g == nullptr || rank < 0 || rank >= g->n || max_lines < c->nlines)
         return set_err(GK_ERR_ARG, "bad local comm args");
     if (cb_on(c)) return set_err(GK_ERR_STATE, "the FP32 basis needs a single-rank context (gk_set_basis_precision)");
+    if (c->pkind == GK_PREC_MG) return set_err(GK_ERR_STATE, "the multigrid preconditioner needs a single-rank context");
     graph_reset(c);
     HIPCHK(hipSetDevice(c->dev));
     c->nranks = g->n;
@@ -538,6 +540,7 @@ int gk_comm_init_xgmi(gk_ctx *c, int nranks, int rank, int max_lines) {
     if (c == nullptr || nranks < 1 || nranks > gk::XS_MAXR || rank < 0 || rank >= nranks || max_lines < c->nlines)
         return set_err(GK_ERR_ARG, "bad xgmi comm args (nranks <= %d)", gk::XS_MAXR);
     if (cb_on(c)) return set_err(GK_ERR_STATE, "the FP32 basis needs a single-rank context (gk_set_basis_precision)");
+    if (c->pkind == GK_PREC_MG) return set_err(GK_ERR_STATE, "the multigrid preconditioner needs a single-rank context");
     graph_reset(c);
     HIPCHK(hipSetDevice(c->dev));
     if (c->comm != nullptr) {  // an RCCL communicator of an abandoned gk_comm_init: the exchange replaces it

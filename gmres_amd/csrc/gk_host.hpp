@@ -36,6 +36,16 @@ struct gk_group {
     std::vector<const double *> ptrs;
 };
 
+// One level of the GK_PREC_MG hierarchy (gk_op.hip: mg_build / mg_apply / mg_free).  lc is a
+// light context -- the level's side, the parent's device and stream, set_geometry and the
+// level's Chebyshev smoother -- that the stencil and the sweeps run on; the vectors are
+// carved from the parent's mg_buf (level 0 smooths on the parent's aux, dA, dB).
+struct gk_mg_level {
+    gk_ctx *lc = nullptr;
+    double *r = nullptr, *e = nullptr;                // level > 0: its input (restricted residual) and result
+    double *z = nullptr, *t = nullptr, *d = nullptr;  // level < L: iterate, residual, post-smoothing correction
+};
+
 struct gk_ctx {
     int dev = 0, N = 0, line0 = 0, nlines = 0, m = 0;
     i64 nloc = 0, ld = 0, g0 = 0;
@@ -70,6 +80,10 @@ struct gk_ctx {
     int cgs_kb = 8;            // CGS2: columns a dots workgroup batches (gk_create: GK_CGS_KB in the environment)
     double *cgs_slab = nullptr, *cgs_s = nullptr;  // CGS2 (lazy): the dots' partials [m][np_pj], s[m]
     i64 cgs_cap = 0;                               // doubles cgs_slab holds
+    std::vector<gk_mg_level> mg;                   // GK_PREC_MG: levels 0 .. L (empty otherwise)
+    double *mg_buf = nullptr;                      // ... their vectors, one allocation
+    int mg_cdeg = 0;                               // ... the coarsest level's sweep count
+    int tune_mg_fused = 1;                         // GK_TUNE_MG_FUSED: residual and restriction in one march
     // decomposition / comm
     int nranks = 1, rank = 0, max_lines = 0;
     int min_lines = 0;  // smallest slab of any rank (0: not gathered yet; ensure_min_lines)
@@ -235,6 +249,12 @@ int op_precond(gk_ctx *c, const double *v, double *out, bool resid, int acc, con
 int op_right(gk_ctx *c, const double *v, double *out, int acc, const double *vdot, double *part);
 int add_precond(gk_ctx *c, const double *t);         // x += M^-1 t, one march where cbpr2 allows
 int add_precond_sweeps(gk_ctx *c, const double *t);  // ... always the sweeps into z, then add_into
+// GK_PREC_MG: the hierarchy of a whole-grid single-rank context (built by gk_set_precond, freed
+// by it and by gk_destroy), the V-cycle behind precond_sweeps, and gk_mg_transfer's launches
+int mg_build(gk_ctx *c, double p0, double p1, int degree);
+void mg_free(gk_ctx *c);
+int mg_apply(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part);
+int mg_transfer(gk_ctx *c, int what, int level, const double *a, const double *b, double *out);
 
 // gk_comm.hip
 bool collective(const gk_ctx *c);

@@ -2,12 +2,14 @@
 // b - A x, M^-1 v, M^-1 A v, A M^-1 v and x += M^-1 t.  What A is and how it is launched
 // is known here and in gk_stencil.hpp (this unit alone includes it, and alone calls
 // gk::cheb_launch); the fused device paths of gk_cheb.hpp and gk_sr.hpp embody the same
-// operator.  Declarations: gk_host.hpp.
+// operator.  The multigrid preconditioner (GK_PREC_MG) is a composition of these launches
+// per level with gk_mg.hpp's transfers.  Declarations: gk_host.hpp.
 #include <algorithm>
 #include <cmath>
 
 #include "gk_cheb.hpp"
 #include "gk_host.hpp"
+#include "gk_mg.hpp"
 #include "gk_stencil.hpp"
 
 namespace gkh __attribute__((visibility("hidden"))) {
@@ -286,9 +288,177 @@ void cheb_coefs(const gk_ctx *c, double *c1, double *c2, double *theta) {
     }
 }
 
-// out = M^-1 in (cbpr2 or Chebyshev sweeps); `in` is read in place (in != out, and
-// for Chebyshev neither is one of the sweeps' work vectors aux, dA, dB).
+// ------------------------------------------------ multigrid (GK_PREC_MG) ---
+// Aggregation multigrid on 2 x 2 blocks: with piecewise-constant P and the 4-member sum
+// P^T, P^T A_N P = 2 A_{N/2} -- every level runs the unscaled stencil on a smaller square
+// grid, so a level is a light context (its side, set_geometry, a Chebyshev smoother) that
+// stencil() and precond_sweeps() run on unchanged, and the cycle is a composition of them
+// with gk_mg.hpp's three streaming launches.
+void mg_free(gk_ctx *c) {
+    for (gk_mg_level &lv : c->mg) delete lv.lc;
+    c->mg.clear();
+    if (c->mg_buf != nullptr) {  // queued cycles may still read it
+        if (c->st != nullptr) (void)hipStreamSynchronize(c->st);
+        (void)hipFree(c->mg_buf);
+    }
+    c->mg_buf = nullptr;
+    c->mg_cdeg = 0;
+}
+
+int mg_build(gk_ctx *c, double p0, double p1, int degree) {
+    mg_free(c);
+    int sides[gk::MG_LMAX];
+    const int nl = gk::mg_levels(c->N, sides);
+    if (nl < 2) return set_err(GK_ERR_ARG, "multigrid needs an even N with N / 2 >= %d (N = %d)", gk::MG_NMIN, c->N);
+    const int L = nl - 1;
+    auto vlen = [](int n) { return ((i64)n * n + 31) / 32 * 32; };  // 256-byte aligned vectors
+    // level 0: z, t, d; between: r, e, z, t, d and the sweeps' aux, dA, dB; coarsest: r, e, aux, dA, dB
+    i64 total = 0;
+    for (int l = 0; l <= L; ++l) total += vlen(sides[l]) * (l == 0 ? 3 : (l < L ? 8 : 5));
+    HIPCHK(hipSetDevice(c->dev));
+    if (hipMalloc(&c->mg_buf, sizeof(double) * (size_t)total) != hipSuccess) {
+        c->mg_buf = nullptr;
+        return set_err(GK_ERR_NOMEM, "cannot allocate the multigrid hierarchy: %.2f GB", total * 8 / 1e9);
+    }
+    // zeroed once: every vector is written before the cycle reads it, but never an uninitialised byte
+    if (hipMemsetAsync(c->mg_buf, 0, sizeof(double) * (size_t)total, c->st) != hipSuccess) {
+        mg_free(c);
+        return set_err(GK_ERR_HIP, "memset failed");
+    }
+    double lo = 0.0, hi = 0.0;
+    c->mg_cdeg = gk::mg_coarse_degree(sides[L], &lo, &hi);
+    double *p = c->mg_buf;
+    auto take = [&](int n) {
+        double *q = p;
+        p += vlen(n);
+        return q;
+    };
+    c->mg.resize(nl);
+    for (int l = 0; l <= L; ++l) {
+        gk_mg_level &lv = c->mg[l];
+        const int n = sides[l];
+        gk_ctx *lc = new gk_ctx();
+        lv.lc = lc;
+        lc->dev = c->dev;
+        lc->N = n;
+        lc->nlines = n;
+        lc->max_lines = n;
+        lc->nloc = (i64)n * n;
+        lc->ld = vlen(n);
+        lc->st = c->st;
+        lc->red = c->red;
+        lc->scal = c->scal;
+        lc->res_cus = c->res_cus;
+        set_geometry(lc);
+        lc->pkind = GK_PREC_CHEB;
+        lc->p0 = l < L ? p0 : lo;
+        lc->p1 = l < L ? p1 : hi;
+        lc->pdeg = l < L ? degree : c->mg_cdeg;
+        if (l > 0) {
+            lv.r = take(n);
+            lv.e = take(n);
+        }
+        if (l < L) {
+            lv.z = take(n);
+            lv.t = take(n);
+            lv.d = take(n);
+        }
+        if (l == 0) {
+            lc->aux = c->aux;
+            lc->dA = c->dA;
+            lc->dB = c->dB;
+        } else {
+            lc->aux = take(n);
+            lc->dA = take(n);
+            lc->dB = take(n);
+        }
+    }
+    return GK_OK;
+}
+
+// out = r - A z on level context lc (OP_RESID's expression with in1 = r)
+static int mg_resid(gk_ctx *lc, const double *z, const double *r, double *out) {
+    gk::StArgs a{};
+    a.x = z;
+    a.in1 = r;
+    a.y = out;
+    return stencil(lc, gk::OP_RESID, gk::ACC_NONE, a);
+}
+
+// rc = P^T (r - A z): one march (GK_TUNE_MG_FUSED), or OP_RESID into t and the plain
+// restriction -- the same expressions in the same order, bit-identical rc.
+static int mg_resid_restrict(gk_ctx *c, gk_mg_level &lv, const double *r, double *rc) {
+    if (c->tune_mg_fused) {
+        HIPCHK(gk::mg_restrict(true, lv.lc->N, lv.z, r, rc, c->st));
+        return GK_OK;
+    }
+    CHK(mg_resid(lv.lc, lv.z, r, lv.t));
+    HIPCHK(gk::mg_restrict(false, lv.lc->N, lv.t, nullptr, rc, c->st));
+    return GK_OK;
+}
+
+// out = MG_0(in): the V-cycle.  Launches on the context's stream only (no allocation, no
+// host synchronisation, no copies), so captured iterations and profiling scopes hold; the
+// closing add of level 0 carries the reduction `acc`.  in and out are none of the
+// hierarchy's vectors nor aux, dA, dB (precond_sweeps' rule).
+int mg_apply(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part) {
+    if (c->mg.size() < 2) return set_err(GK_ERR_STATE, "multigrid hierarchy not built");
+    ProfScope ps(c, GK_KID_PREC);
+    const int L = (int)c->mg.size() - 1;
+    for (gk_mg_level &lv : c->mg) {  // the smoothers follow the parent's Chebyshev route
+        lv.lc->tune_cheb_fused = c->tune_cheb_fused;
+        lv.lc->st = c->st;
+    }
+    for (int l = 0; l < L; ++l) {  // pre-smoothing from zero, residual, restriction
+        gk_mg_level &lv = c->mg[l];
+        const double *r = l == 0 ? in : lv.r;
+        CHK(precond_sweeps(lv.lc, r, lv.z, gk::ACC_NONE, nullptr, nullptr));
+        CHK(mg_resid_restrict(c, lv, r, c->mg[l + 1].r));
+    }
+    CHK(precond_sweeps(c->mg[L].lc, c->mg[L].r, c->mg[L].e, gk::ACC_NONE, nullptr, nullptr));
+    for (int l = L - 1; l >= 0; --l) {  // correction, post-smoothing on the new residual
+        gk_mg_level &lv = c->mg[l];
+        gk_ctx *lc = lv.lc;
+        const double *r = l == 0 ? in : lv.r;
+        HIPCHK(gk::mg_prolong_add(lc->N, lv.z, c->mg[l + 1].e, lv.z, c->st));
+        CHK(mg_resid(lc, lv.z, r, lv.t));
+        CHK(precond_sweeps(lc, lv.t, lv.d, gk::ACC_NONE, nullptr, nullptr));
+        HIPCHK(gk::mg_add(l == 0 ? acc : gk::ACC_NONE, lc->nblk_stream, lc->nloc, lv.z, lv.d, l == 0 ? out : lv.e,
+                          vdot, part, c->st));
+    }
+    if (acc != gk::ACC_NONE) c->last_np = c->mg[0].lc->nblk_stream;
+    return GK_OK;
+}
+
+// gk_mg_transfer's launches between level `level` and the next, host arrays staged through
+// the hierarchy's own vectors.
+int mg_transfer(gk_ctx *c, int what, int level, const double *a, const double *b, double *out) {
+    gk_mg_level &f = c->mg[level], &g = c->mg[level + 1];
+    const int N = f.lc->N;
+    const size_t nf = sizeof(double) * (size_t)f.lc->nloc, nc = sizeof(double) * (size_t)g.lc->nloc;
+    if (what == 2) {  // out = a + P b, in place as the cycle runs it
+        HIPCHK(hipMemcpyAsync(f.z, a, nf, hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemcpyAsync(g.e, b, nc, hipMemcpyHostToDevice, c->st));
+        HIPCHK(gk::mg_prolong_add(N, f.z, g.e, f.z, c->st));
+        HIPCHK(hipMemcpyAsync(out, f.z, nf, hipMemcpyDeviceToHost, c->st));
+        return sync_st(c);
+    }
+    HIPCHK(hipMemcpyAsync(f.t, a, nf, hipMemcpyHostToDevice, c->st));
+    if (what == 1) {  // out = P^T (a - A b) by the fused march
+        HIPCHK(hipMemcpyAsync(f.z, b, nf, hipMemcpyHostToDevice, c->st));
+        HIPCHK(gk::mg_restrict(true, N, f.z, f.t, g.r, c->st));
+    } else {  // out = P^T a
+        HIPCHK(gk::mg_restrict(false, N, f.t, nullptr, g.r, c->st));
+    }
+    HIPCHK(hipMemcpyAsync(out, g.r, nc, hipMemcpyDeviceToHost, c->st));
+    return sync_st(c);
+}
+
+// out = M^-1 in (cbpr2, Chebyshev sweeps or the multigrid cycle); `in` is read in place
+// (in != out, and for Chebyshev and multigrid neither is one of the sweeps' work vectors
+// aux, dA, dB).
 int precond_sweeps(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part) {
+    if (c->pkind == GK_PREC_MG) return mg_apply(c, in, out, acc, vdot, part);
     bool fused = false;
     if (c->pkind == GK_PREC_CHEB) CHK(cheb_fused_ok(c, &fused));
     if (!fused) CHK(halo(c, in));  // the fused passes bring their own deep halos

@@ -14,7 +14,7 @@
 !!   gmres_hip_c           ISO_C_BINDING interfaces to include/gmres_hip.h
 !!   gmres_hip_interfaces  the reference's two abstract plug-in interfaces
 !!   gmres_hip             device-backed plug-ins (hip_poisson5, hip_identity,
-!!                         hip_cbpr2, hip_chebyshev), drop-in solvers
+!!                         hip_cbpr2, hip_chebyshev, hip_mg), drop-in solvers
 !!                         gmres_mgsr_hip / gmres_hh_hip / gmres_hh_prec_hip,
 !!                         and bind(C) drivers for harnesses that already hold
 !!                         a device context (gmres_mgsr_hip_run, gmres_hh_hip_run).
@@ -23,7 +23,7 @@ module gmres_hip_c
     use, intrinsic :: iso_c_binding
     implicit none
     integer(c_int), parameter :: GK_OK = 0
-    integer(c_int), parameter :: GK_PREC_IDENTITY = 0, GK_PREC_CBPR2 = 1, GK_PREC_CHEB = 2
+    integer(c_int), parameter :: GK_PREC_IDENTITY = 0, GK_PREC_CBPR2 = 1, GK_PREC_CHEB = 2, GK_PREC_MG = 3
     integer(c_int), parameter :: GK_SIDE_LEFT = 0, GK_SIDE_RIGHT = 1
     integer(c_int), parameter :: GK_BASIS_F64 = 0, GK_BASIS_F32 = 1
     integer(c_int), parameter :: GK_ORTH_MGSR = 0, GK_ORTH_CGS2 = 1
@@ -317,12 +317,14 @@ module gmres_hip
     integer, public :: hip_device = 0
     !> Chebyshev(k) degree used by hip_chebyshev when params(3) is absent
     integer, public :: hip_cheb_degree = 8
+    !> smoother degree used by hip_mg when params(3) is absent
+    integer, public :: hip_mg_degree = 2
     integer, parameter, public :: MGSR_OMP = 1, MGSR_MF = 0
 
     public :: stencil_vector, precond
     public :: GK_SIDE_LEFT, GK_SIDE_RIGHT, GK_BASIS_F64, GK_BASIS_F32, GK_ORTH_MGSR, GK_ORTH_CGS2
     public :: GK_HH_PREC_NONE, GK_HH_PREC_LEFT, GK_HH_PREC_RIGHT
-    public :: hip_poisson5, hip_identity, hip_cbpr2, hip_chebyshev
+    public :: hip_poisson5, hip_identity, hip_cbpr2, hip_chebyshev, hip_mg
     public :: gmres_mgsr_hip, gmres_hh_hip, gmres_hh_prec_hip, hip_release
     public :: pcg_hip, pbicgstab_hip, pcg_drive, bicgstab_drive, pcg_drive_seq, bicgstab_drive_seq
     !> iterations queued per chunk by the fused short-recurrence drivers
@@ -851,6 +853,27 @@ contains
         if (size(params) >= 3) k = nint(params(3))
     end function cheb_degree
 
+    !> Aggregation multigrid V-cycle (beyond the reference; include/gmres_hip.h GK_PREC_MG):
+    !> Chebyshev(k) smoothing on [params(1), params(2)] on every level, k = params(3) if
+    !> given (default hip_mg_degree = 2); even n with n / 2 >= 8.  Symmetric positive
+    !> definite: for pcg_hip as well as the GMRES drivers and pbicgstab_hip.
+    subroutine hip_mg(A_x, r, z, aux, params, n)
+        procedure(stencil_vector) :: A_x
+        real(8), intent(in) :: r(:)
+        real(8), intent(out) :: z(:), aux(:)
+        real(8), intent(in) :: params(:)
+        integer, intent(in) :: n
+        call require_device_op(A_x, 'hip_mg')
+        call apply_prec(GK_PREC_MG, params, int(mg_degree(params), c_int), r, z, n)
+        aux = 0.0d0
+    end subroutine hip_mg
+
+    integer function mg_degree(params) result(k)
+        real(8), intent(in) :: params(:)
+        k = hip_mg_degree
+        if (size(params) >= 3) k = nint(params(3))
+    end function mg_degree
+
     subroutine prec_kind(M_inv, params, kind, degree)
         procedure(precond) :: M_inv
         real(8), intent(in) :: params(:)
@@ -863,8 +886,11 @@ contains
         else if (c_associated(c_funloc(M_inv), c_funloc(hip_chebyshev))) then
             kind = GK_PREC_CHEB
             degree = int(cheb_degree(params), c_int)
+        else if (c_associated(c_funloc(M_inv), c_funloc(hip_mg))) then
+            kind = GK_PREC_MG
+            degree = int(mg_degree(params), c_int)
         else
-            write (*, '(A)') 'gmres_hip: M_inv must be hip_identity, hip_cbpr2 or hip_chebyshev'
+            write (*, '(A)') 'gmres_hip: M_inv must be hip_identity, hip_cbpr2, hip_chebyshev or hip_mg'
             error stop 2
         end if
     end subroutine prec_kind

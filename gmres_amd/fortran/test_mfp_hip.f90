@@ -10,32 +10,34 @@
 !! stored as FP32); `cgs2` runs it alone with the CGS2 Arnoldi step (orth = GK_ORTH_CGS2);
 !! `hhright` runs the Householder solve alone, preconditioned on the
 !! right (gmres_hh_prec_hip(..., side = GK_SIDE_RIGHT)), and prints its final residual
-!! a second time with every digit.
+!! a second time with every digit; `mg` runs the MGS-R solve alone with the multigrid
+!! V-cycle hip_mg on the right (smoother interval (8, 1), tol 1e-12), then pcg_hip with it.
 program test_mfp_hip
     use gmres_hip
     implicit none
     integer :: nsize, max_iter, n_args
     character(len=32) :: arg_str
-    logical :: right, f32, hhright, cgs2
+    logical :: right, f32, hhright, cgs2, mg
     n_args = command_argument_count()
     if (n_args < 2) then
-        print *, "usage ./test_mfp_hip <grid size> <iterations per restart> [right|f32|cgs2|hhright]"
+        print *, "usage ./test_mfp_hip <grid size> <iterations per restart> [right|f32|cgs2|hhright|mg]"
         stop
     end if
-    right = .false.; f32 = .false.; hhright = .false.; cgs2 = .false.
+    right = .false.; f32 = .false.; hhright = .false.; cgs2 = .false.; mg = .false.
     if (n_args >= 3) then
         call get_command_argument(3, arg_str)
         right = trim(arg_str) == 'right'
         f32 = trim(arg_str) == 'f32'
         cgs2 = trim(arg_str) == 'cgs2'
         hhright = trim(arg_str) == 'hhright'
+        mg = trim(arg_str) == 'mg'
     end if
     call get_command_argument(1, arg_str)
     read (arg_str, *) nsize
     call get_command_argument(2, arg_str)
     read (arg_str, *) max_iter
     write (*, '(60("-"))')
-    if (.not. right .and. .not. f32 .and. .not. cgs2) then
+    if (.not. right .and. .not. f32 .and. .not. cgs2 .and. .not. mg) then
         call run(nsize, max_iter, .true.)
         write (*, '(60("-"))')
     end if
@@ -43,8 +45,29 @@ program test_mfp_hip
         call run(nsize, max_iter, .false.)
         write (*, '(60("-"))')
     end if
+    if (mg) then
+        call run_pcg_mg(nsize)
+        write (*, '(60("-"))')
+    end if
     call hip_release()
 contains
+    subroutine run_pcg_mg(nsize)
+        integer, intent(in) :: nsize
+        real(8), allocatable :: b(:), x(:)
+        real(8) :: params(2), res
+        integer :: iter
+        allocate (b(nsize*nsize), x(nsize*nsize))
+        params = [8.0d0, 1.0d0]
+        x = 1.0d0
+        call hip_poisson5(x, b, nsize)
+        iter = 200
+        write (*, '(A)') 'PCG Poisson 2D Test Matrix Free (multigrid V-cycle, MI355X)'
+        call pcg_hip(hip_poisson5, b, x, 1.d-10, iter, res, hip_mg, params)
+        write (*, '(A30, I8)') 'PCG iterations:', iter
+        write (*, '(A30, ES12.4)') 'PCG residual:', res
+        write (*, '(A30, ES12.4)') 'PCG max error L_max:', maxval(abs(x - 1.0d0))
+    end subroutine run_pcg_mg
+
     subroutine run(nsize, max_iter, householder)
         integer, intent(in) :: nsize, max_iter
         logical, intent(in) :: householder
@@ -54,6 +77,10 @@ contains
         tol = 1.d-15
         allocate (b(nsize*nsize), x(nsize*nsize), params(2))
         params(1) = 8.2d0; params(2) = 0.2d0
+        if (mg) then
+            tol = 1.d-12
+            params(1) = 8.0d0; params(2) = 1.0d0
+        end if
         x = 1.0d0
         call hip_poisson5(x, b, nsize)   ! b = A*1: every solution entry must be 1.0
         if (householder .and. hhright) then
@@ -66,6 +93,8 @@ contains
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR Chebyshev, compressed basis, MI355X)'
         else if (cgs2) then
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (CGS2 Chebyshev, MI355X)'
+        else if (mg) then
+            write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR multigrid V-cycle on the right, MI355X)'
         else
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR Chebyshev, MI355X)'
         end if
@@ -85,6 +114,9 @@ contains
         else if (cgs2) then
             call gmres_mgsr_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params, &
                                 orth=GK_ORTH_CGS2)
+        else if (mg) then
+            call gmres_mgsr_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_mg, params, &
+                                side=GK_SIDE_RIGHT)
         else
             call gmres_mgsr_hip(hip_poisson5, b, x, max_iter, tol, errn, verr, n_iter, n_stages, hip_cbpr2, params)
         end if

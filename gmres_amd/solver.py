@@ -18,7 +18,11 @@ import numpy as np
 from . import _native as nat
 
 PREC = {"identity": nat.GK_PREC_IDENTITY, "none": nat.GK_PREC_IDENTITY,
-        "cbpr2": nat.GK_PREC_CBPR2, "cheb": nat.GK_PREC_CHEB, "chebyshev": nat.GK_PREC_CHEB}
+        "cbpr2": nat.GK_PREC_CBPR2, "cheb": nat.GK_PREC_CHEB, "chebyshev": nat.GK_PREC_CHEB,
+        "mg": nat.GK_PREC_MG, "multigrid": nat.GK_PREC_MG}
+# (params, degree) a kind takes where the caller gives none
+PREC_DEFAULTS = {nat.GK_PREC_MG: ((8.0, 1.0), 2)}
+PREC_DEFAULT = ((8.2, 0.2), 8)
 SIDE = {"left": nat.GK_SIDE_LEFT, "right": nat.GK_SIDE_RIGHT}
 BASIS = {"f64": nat.GK_BASIS_F64, "f32": nat.GK_BASIS_F32}
 ORTH = {"mgsr": nat.GK_ORTH_MGSR, "cgs2": nat.GK_ORTH_CGS2}
@@ -188,15 +192,20 @@ class Context:
         return True
 
     # -- problem setup ---------------------------------------------------
-    def set_precond(self, kind: str | int = "identity", params=(8.2, 0.2), degree: int = 8,
+    def set_precond(self, kind: str | int = "identity", params=None, degree: int | None = None,
                     side: str = "left") -> None:
         """side "left" (the reference's MGS-R) or "right": w = A M^-1 v_j and
         x += M^-1 (V y), so final_err is the true relative residual
         (gk_set_precond_side; the MGS-R cycle's side -- gmres_hh takes its own,
-        precondition="right")."""
+        precondition="right").  params / degree left out: (8.2, 0.2) and 8; for "mg"
+        (the aggregation multigrid V-cycle: whole grid on one rank, even N >= 16) the
+        smoother's interval (8.0, 1.0) and degree 2."""
         k = PREC[kind] if isinstance(kind, str) else int(kind)
         if side not in SIDE:
             raise ValueError(f"side must be 'left' or 'right', not {side!r}")
+        dpar, ddeg = PREC_DEFAULTS.get(k, PREC_DEFAULT)
+        params = dpar if params is None else params
+        degree = ddeg if degree is None else degree
         pr = np.ascontiguousarray(params, dtype=np.float64)
         nat.check(nat.hip().gk_set_precond(self._h, k, _p(pr), pr.size, int(degree)), "gk_set_precond")
         if side != self.side:  # a change of side ends an open cycle; the same side is no call at all
@@ -373,6 +382,25 @@ class Context:
         name (None = launch per projection), workgroups, chunk split."""
         return _res_dict(lambda buf: nat.hip().gk_res_info(self._h, int(hh), buf), "gk_res_info")
 
+    def mg_info(self) -> dict:
+        """The live multigrid hierarchy (gk_mg_info; the preconditioner must be "mg"):
+        mg_plan(N)'s keys with "degree" the smoother's."""
+        return _mg_dict(lambda buf: nat.hip().gk_mg_info(self._h, buf), "gk_mg_info")
+
+    def mg_transfer(self, what: int, level: int, a: np.ndarray, b: np.ndarray | None = None) -> np.ndarray:
+        """Transfers between level `level` and the next of the multigrid hierarchy on host
+        arrays (gk_mg_transfer; diagnostic): what 0: P^T a, 1: P^T (a - A b) by the fused
+        march, 2: a + P b.  Ends an open cycle."""
+        sides = self.mg_info()["sides"]
+        nf, nc = sides[level] ** 2, sides[level + 1] ** 2
+        aa = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        bb = None if b is None else np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+        assert aa.size == nf and (bb is None or bb.size == (nc if what == 2 else nf))
+        out = np.empty(nf if what == 2 else nc)
+        nat.check(nat.hip().gk_mg_transfer(self._h, int(what), int(level), _p(aa), None if bb is None else _p(bb),
+                                           _p(out)), "gk_mg_transfer")
+        return out
+
     def tune(self, key: int, value: int) -> None:
         """Launch-policy knob (include/gmres_hip.h GK_TUNE_*)."""
         nat.check(nat.hip().gk_set_tuning(self._h, int(key), int(value)), "gk_set_tuning")
@@ -403,6 +431,24 @@ def res_plan_query(nloc: int, cus: int = 256, share: int = 1, hh: bool = False, 
     return _res_dict(lambda buf: nat.hip().gk_res_plan_query(int(nloc), int(cus), int(share), int(hh), int(nt),
                                                              int(block), buf),
                      "gk_res_plan_query")
+
+
+def _mg_dict(call, what: str) -> dict:
+    buf = (ctypes.c_int * nat.GK_MG_INFO_LEN)()
+    nat.check(call(buf), what)
+    nl = int(buf[0])
+    d = {"levels": nl, "coarse_degree": int(buf[1]), "sides": [int(v) for v in buf[3:3 + nl]]}
+    if buf[2] > 0:
+        d["degree"] = int(buf[2])
+    return d
+
+
+def mg_plan(N: int) -> dict:
+    """The multigrid hierarchy of an N x N grid (gk_mg_plan_query: host-only, no GPU
+    touched): "levels" (L + 1), "sides" N_0 .. N_L (halved while even and >= 16) and
+    "coarse_degree" (the last level's Chebyshev sweeps); a context's mg_info() adds its
+    smoother's "degree"."""
+    return _mg_dict(lambda buf: nat.hip().gk_mg_plan_query(int(N), buf), "gk_mg_plan_query")
 
 
 def cb_plan_query(nloc: int, cus: int = 256, share: int = 1, m: int = 95) -> dict:

@@ -44,6 +44,7 @@ extern "C" {
 #define GK_PREC_IDENTITY 0 /* z = r ; config 1 "no precond"  */
 #define GK_PREC_CBPR2 1    /* src/preconds/chebyshev.f90:8-38, params(1:2) */
 #define GK_PREC_CHEB 2     /* Chebyshev(k) semi-iteration, build-defined (BASELINE config 3) */
+#define GK_PREC_MG 3       /* aggregation multigrid V-cycle, Chebyshev(degree) smoothing (beyond the reference) */
 
 /* Kernel ids for gk_profile_read(). */
 #define GK_KID_PROJ 0    /* fused MGS-R / Householder projection (axpy_i + dot_{i+1}) */
@@ -53,7 +54,7 @@ extern "C" {
 #define GK_KID_COMM 4    /* all-reduce / broadcast (RCCL, local group or device exchange) */
 #define GK_KID_OTHER 5
 #define GK_KID_RES 6     /* resident MGS-R step: whole cascade + norm + scale in one launch */
-#define GK_KID_PREC 7    /* temporal-blocked Chebyshev(k) passes (k_cheb_fused) */
+#define GK_KID_PREC 7    /* temporal-blocked Chebyshev(k) passes (k_cheb_fused); GK_PREC_MG: one whole V-cycle */
 #define GK_KID_HALO 8    /* halo lines with the slab neighbours (RCCL send/recv, local group or device exchange) */
 #define GK_KID_GRAPH 9   /* one launch-path MGS-R step replayed as a hipGraph (its 2j projections, all-reduces, scale) */
 /* short-recurrence passes (gk_sr_*): GK_KID_SR + the pass kind of gk_sr.hpp --
@@ -155,8 +156,41 @@ int gk_peer_info(int device, int peer, int *can_access, int *link_type, int *hop
 int gk_comm_latency(gk_ctx *ctx, int iters, double *allreduce_us, double *halo_us);
 
 /* Preconditioner: kind GK_PREC_*, params (cbpr2: params[0..1] as
- * chebyshev.f90:19-25; CHEB: interval ends params[0..1]), degree (CHEB only). */
+ * chebyshev.f90:19-25; CHEB: interval ends params[0..1]), degree (CHEB and MG).
+ *
+ * GK_PREC_MG: a V-cycle of aggregation multigrid on 2 x 2 blocks for the 5-point operator.
+ * With piecewise-constant prolongation P and the 4-member sum P^T, P^T A_N P = 2 A_{N/2}:
+ * every level runs the same unscaled stencil on a smaller square grid (the geometric
+ * choice -- twice the Galerkin correction, the classical over-correction of unsmoothed
+ * aggregates).  Levels: N_0 = N; while N_l is even and N_l / 2 >= 8, N_{l+1} = N_l / 2.
+ * On every level but the last, with Cheb = Chebyshev(degree) on params[0..1] from zero:
+ *   z = Cheb(r); rc = P^T (r - A z); z += P MG_{l+1}(rc); out = z + Cheb(r - A z).
+ * The last level is Chebyshev(nu_c) on its exact spectrum interval, nu_c the smallest
+ * degree in 1..64 whose error bound 1 / cosh((nu + 1) acosh sigma) is <= 0.1 (capped at
+ * 64: grids with few factors of two, e.g. 514 -> 257, get a weak coarse solve and more
+ * iterations).  Symmetric positive definite: it serves PCG as well as GMRES / BiCGSTAB,
+ * on either side.  The hierarchy is built here and freed by gk_destroy or the next
+ * gk_set_precond.  GK_ERR_ARG: odd N or N / 2 < 8, a degree outside 1..8, an empty
+ * interval.  GK_ERR_STATE: a context that is not the whole grid on one rank (any
+ * communicator, line0 != 0, nlines != N); gk_comm_init* on an MG context return the same.
+ * The stateless gk_precond_apply has no multigrid (GK_ERR_ARG). */
 int gk_set_precond(gk_ctx *ctx, int kind, const double *params, int nparams, int degree);
+/* The multigrid hierarchy.  info (GK_MG_INFO_LEN ints): [0] the number of levels L + 1,
+ * [1] the last level's sweep count nu_c, [2] the smoother degree (gk_mg_info; 0 from the
+ * plan query), [3 .. 3 + L] the level sides N_0 .. N_L, zeros after.
+ * gk_mg_plan_query: pure host, for a grid of side nside; no device is touched.
+ * gk_mg_info: the live hierarchy of a context whose preconditioner is GK_PREC_MG
+ * (GK_ERR_STATE otherwise).
+ * gk_mg_transfer: diagnostic / test hook on host arrays between level `level` and the
+ * next (f = N_level^2, c = N_{level+1}^2 doubles) of an MG context --
+ *   what 0  out(c) = P^T a(f)                  the plain restriction
+ *   what 1  out(c) = P^T (a(f) - A b(f))       the fused residual-restriction march
+ *   what 2  out(f) = a(f) + P b(c)             the prolongation
+ * It overwrites the hierarchy's work vectors and ends an open cycle, as gk_apply does. */
+#define GK_MG_INFO_LEN 35
+int gk_mg_plan_query(int nside, int *info);
+int gk_mg_info(gk_ctx *ctx, int *info);
+int gk_mg_transfer(gk_ctx *ctx, int what, int level, const double *a, const double *b, double *out);
 /* Side of the preconditioner in the MGS-R cycle (context state; default left; kept
  * across gk_set_precond).
  *   GK_SIDE_LEFT   the reference: w = M^-1 A V(:,j), and the host's stopping quantity
@@ -635,7 +669,12 @@ int gk_res_info(gk_ctx *ctx, int hh, long long *info);
  *                          accumulating output, x += M^-1 t in one launch; 0 the sweep into a
  *                          work vector, then the add.  Bit-identical x
  *   GK_TUNE_SPIN_WAIT      1 (default): gk_mgs_step_wait / gk_hh_step_wait spin on the step's
- *                          event; 0: hipEventSynchronize (may sleep in the driver per step) */
+ *                          event; 0: hipEventSynchronize (may sleep in the driver per step)
+ *   GK_TUNE_MG_FUSED       1 (default): the multigrid cycle forms each level's restricted
+ *                          residual P^T (r - A z) in one line march (z and r read, a quarter
+ *                          vector written, the residual never stored); 0: the residual
+ *                          stencil into a work vector, then the plain restriction.
+ *                          Bit-identical results */
 #define GK_TUNE_PROJ_NT 0
 #define GK_TUNE_PROJ_BLOCKS 1
 #define GK_TUNE_STENCIL_BLOCKS 2
@@ -663,6 +702,7 @@ int gk_res_info(gk_ctx *ctx, int hh, long long *info);
 #define GK_TUNE_RES_PIPE 30
 #define GK_TUNE_RIGHT_FUSED 31
 #define GK_TUNE_RES_PIPE_CARRY 32
+#define GK_TUNE_MG_FUSED 33 /* GK_PREC_MG contexts only */
 int gk_set_tuning(gk_ctx *ctx, int key, int value);
 /* Test hook: hold = 1 enqueues on the context's stream a wait for a mapped host
  * word that only hold = 0 writes (hipStreamWaitValue32) -- every later kernel of
