@@ -26,11 +26,13 @@ HIP_SO = os.path.join(LIB, "libgmres_hip.so")
 FHOST_SO = os.path.join(LIB, "libgmres_fhost.so")
 DRIVER = os.path.join(LIB, "test_mfp_hip")
 
-# Translation units compiled in parallel, one per subsystem: the C-ABI and the
-# streaming kernels (gk_api), the operator and preconditioner launches with the stencil
-# kernels (gk_op), the Chebyshev pass split by level count, the blocked and the strict
-# resident steps (gk_blk, gk_resident), the collectives (gk_comm), the short-recurrence
-# solvers (gk_sr_api), the compressed-basis step (gk_cb) and the CGS2 step (gk_cgs).
+# Translation units compiled in parallel, one per subsystem: the C-ABI's context, tuning,
+# profiling and stateless entries (gk_api), the Arnoldi launches with the streaming kernels
+# and the MGS-R cycle (gk_step), the Householder cycle (gk_hh), the operator and
+# preconditioner launches with the stencil kernels (gk_op), the Chebyshev pass split by
+# level count, the blocked and the strict resident steps (gk_blk, gk_resident), the
+# collectives (gk_comm), the short-recurrence solvers (gk_sr_api), the compressed-basis
+# step (gk_cb) and the CGS2 step (gk_cgs).
 # Seconds per unit, one compile at a time on an 8-core build machine: gk_api 7,
 # gk_cheb0..3 26-31, gk_blk 15, gk_resident 42-48 (the unrolled resident kernels),
 # gk_comm 4, gk_sr_api 8; the single gk_api unit they were split from took 47-60.
@@ -44,20 +46,21 @@ def _unit(unit: str) -> tuple[str, list[str], str]:
 
 # (source, extra defines, object name): the Chebyshev pass in GK_CF_PARTS parts
 GK_CF_PARTS = 4
-HIP_UNITS = ([_unit("gk_api"), _unit("gk_op")]
+HIP_UNITS = ([_unit("gk_api"), _unit("gk_step"), _unit("gk_hh"), _unit("gk_op")]
              + [(_src("gk_cheb"), [f"GK_CF_PART={p}"], f"gk_cheb{p}.o") for p in range(GK_CF_PARTS)]
              + [_unit(u) for u in ("gk_blk", "gk_resident", "gk_comm", "gk_sr_api")])
 # ... and the unit of the opt-in FP32-compressed basis: its resident step, scale and widening copy (its
-# launch-path projection, x update and Gram are float instantiations in gk_api's unit); HIP_UNITS stays
+# launch-path projection, x update and Gram are float instantiations in gk_step's unit); HIP_UNITS stays
 # the FP64 solvers' list
 HIP_UNITS_CB = [_unit("gk_cb")]
-# ... and the unit of the opt-in CGS2 Arnoldi step (batched dots, reduce, j-column AXPY): twelve in all
+# ... and the unit of the opt-in CGS2 Arnoldi step (batched dots, reduce, j-column AXPY): fourteen in all
 HIP_UNITS_CGS = [_unit("gk_cgs")]
-# ... and the unit of the multigrid preconditioner's transfer and closing kernels: thirteen with it
+# ... and the unit of the multigrid preconditioner's transfer and closing kernels: fifteen with it
 HIP_UNITS_MG = [_unit("gk_mg")]
 HIP_UNITS_ALL = HIP_UNITS + HIP_UNITS_CB + HIP_UNITS_CGS + HIP_UNITS_MG
 HIP_SOURCES = sorted({u[0] for u in HIP_UNITS_ALL})
-HIP_HEADERS = [os.path.join(CSRC, h) for h in ("gk_common.hpp", "gk_kernels.hpp", "gk_stencil.hpp", "gk_cheb.hpp", "gk_res.hpp",
+HIP_HEADERS = [os.path.join(CSRC, h) for h in ("gk_common.hpp", "gk_kernels.hpp", "gk_step_kernels.hpp",
+                                                "gk_hh_kernels.hpp", "gk_stencil.hpp", "gk_cheb.hpp", "gk_res.hpp",
                                                 "gk_blk.hpp", "gk_sr.hpp", "gk_host.hpp", "gk_resident.hpp",
                                                 "gk_cb.hpp", "gk_cgs.hpp", "gk_mg.hpp")]
 HIP_DEPS = HIP_SOURCES + HIP_HEADERS + [os.path.join(ROOT, "include", "gmres_hip.h")]

@@ -2,7 +2,7 @@
 // gk_set_basis_precision GK_BASIS_F32): the resident step k_mgs_wcb, its planner and
 // launcher, and the two launch-path kernels that exist on float columns only (the scale
 // that writes the column, the widening copy).  The launch path's projection, x update and
-// Gram are the float instantiations of gk_kernels.hpp's k_proj / k_update_x / k_gram.
+// Gram are the float instantiations of gk_step_kernels.hpp's k_proj / k_update_x / k_gram.
 //
 // The basis is STORED in FP32; w, every dot, every AXPY, the H column and x stay FP64.
 // A column element is widened exactly on load, and the FP64 expressions and their order

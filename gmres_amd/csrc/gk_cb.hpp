@@ -51,7 +51,7 @@ GK_HIDDEN int cb_launch(const CbPlan &p, const ResArgs &a, float *F, double *vjw
                         std::string &msg);
 
 // The launch path's two kernels of float columns alone (each returns hipGetLastError() of
-// its launch; projection, x update and Gram: k_proj / k_update_x / k_gram<float>, gk_kernels.hpp).
+// its launch; projection, x update and Gram: k_proj / k_update_x / k_gram<float>, gk_step_kernels.hpp).
 // out = float(w / h), h = sqrt(sum(pin)), the same values widened to vjw (and to v1w unless nullptr)
 GK_HIDDEN hipError_t cb_scale(int blocks, float *out, double *vjw, double *v1w, const double *w, const double *pin,
                               int npin, double *hslot, i64 n, double *hcopy, const double *hsrc, int ncopy,

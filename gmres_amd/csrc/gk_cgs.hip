@@ -1,6 +1,6 @@
 // gk_cgs.hip -- the CGS2 Arnoldi step's kernels for gfx950 (gk_cgs.hpp).
 //
-// All three are HBM-bandwidth bound and follow gk_kernels.hpp's rules: double2 accesses
+// All three are HBM-bandwidth bound and follow gk_step_kernels.hpp's rules: double2 accesses
 // along the vector, one partial per workgroup into a fixed slab that the next launch
 // re-reduces in a fixed order, the odd-length tail element on thread 0 of workgroup 0,
 // and -ffp-contract=off so that every element-wise expression is the stated one.

@@ -4,7 +4,7 @@
 //   cgs_dots    slab[k][b] = workgroup b's partial of <w, V_k>, k < j, every dot on the same w
 //   cgs_reduce  s[k] = sum_b slab[k][b] in a fixed order (N ranks: all-reduced afterwards)
 //   cgs_axpy    w_e = ((w_e - s_1 V_1,e) - s_2 V_2,e) .. - s_j V_j,e, H(k,j) (+)= s_k
-// -- with no atomics, no grid barrier and no spin wait; gk_api.hip's cgs_chain strings two
+// -- with no atomics, no grid barrier and no spin wait; gk_step.hip's cgs_chain strings two
 // sweeps and the closing scale together.
 #pragma once
 #include "gk_common.hpp"

@@ -1,7 +1,7 @@
 // gk_common.hpp -- definitions shared by every translation unit (gk_api.hip: the
-// context and the Arnoldi steps; gk_comm.hip: the collectives; gk_resident.hip and
-// gk_blk.hip: the resident steps; gk_sr_api.hip: the short-recurrence solvers;
-// gk_cheb.hip: the Chebyshev pass).
+// context; gk_step.hip and gk_hh.hip: the Arnoldi steps; gk_comm.hip: the collectives;
+// gk_resident.hip and gk_blk.hip: the resident steps; gk_sr_api.hip: the short-recurrence
+// solvers; gk_cheb.hip: the Chebyshev pass).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -132,6 +132,46 @@ __device__ __forceinline__ void st_vec(double *p, const double (&v)[VEC]) {
 
 // Fused reductions of a pass: none, <y, vdot>, or <y, y>.
 enum { ACC_NONE = 0, ACC_DOT = 1, ACC_NORM = 2 };
+
+// What one k_proj launch does (gk_step_kernels.hpp; the callers of gk_host.hpp's proj name it).
+enum { PJ_DOT = 0, PJ_AXPY = 1, PJ_AXPY_DOT = 2, PJ_AXPY_NORM = 3 };
+
+constexpr int GCMAX = 128;  // most columns of a Gram diagnostic (k_gram; sizes the pinned read-back buffer)
+
+// --------------------------------------------------------------------------
+// Reference-order dots for the orthogonality diagnostics (gmres_mgsr.f90:414-420,
+// gmres_hh.f90:568-593).  Fortran dot_product is ONE running sum
+// h = h + a(k)*b(k), k = 1..n.  Both diagnostics measure rounding noise, and
+// the reference's figure is dominated by that running sum's own rounding, so
+// the device evaluates them the same way: one lane per dot, k in order,
+// multiply then add (-ffp-contract=off) -- bit-identical to the reference's
+// formula on the same basis.  n dependent adds per lane: slow by design, run
+// once per solve (the tree-reduced k_gram is the fast alternative).  Its two
+// kernels: k_seqdot_pairs (gk_step_kernels.hpp), k_hh_rebuild_dot (gk_hh_kernels.hpp).
+// --------------------------------------------------------------------------
+constexpr int SQ_B = 8;  // double2 per column in flight per lane
+
+__device__ __forceinline__ double seq_dot(const double *__restrict__ a, const double *__restrict__ b, i64 n) {
+    const double2 *a2 = reinterpret_cast<const double2 *>(a), *b2 = reinterpret_cast<const double2 *>(b);
+    const i64 n2 = n >> 1;
+    double h = 0.0;
+    i64 e = 0;
+    for (; e + SQ_B <= n2; e += SQ_B) {
+        double2 x[SQ_B], y[SQ_B];
+#pragma unroll
+        for (int u = 0; u < SQ_B; ++u) {
+            x[u] = a2[e + u];
+            y[u] = b2[e + u];
+        }
+#pragma unroll
+        for (int u = 0; u < SQ_B; ++u) {
+            h = h + x[u].x * y[u].x;
+            h = h + x[u].y * y[u].y;
+        }
+    }
+    for (i64 k = 2 * e; k < n; ++k) h = h + a[k] * b[k];
+    return h;
+}
 
 // A kernel launched with `lds` bytes of dynamic LDS needs that size allowed first.
 // hipFuncSetAttribute is per device: memo[ATTR_DEVS] (one per kernel instantiation)

@@ -1,6 +1,6 @@
 // gk_host.hpp -- internal header of the host-side units of libgmres_hip.so
-// (gk_api.hip, gk_op.hip, gk_comm.hip, gk_sr_api.hip); never installed.  The context, the
-// error / check macros, the profiling scope and the few helpers that cross units.
+// (gk_api.hip, gk_step.hip, gk_hh.hip, gk_op.hip, gk_comm.hip, gk_sr_api.hip); never installed.
+// The context, the error / check macros, the profiling scope and the helpers that cross units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -19,6 +19,8 @@ using gk::i64;
 namespace gk {
 struct SrDev;
 struct SrMirror;
+struct ResPlan;  // gk_resident.hpp
+struct CbPlan;   // gk_cb.hpp
 }  // namespace gk
 
 // In-process communicator: several contexts of one process (e.g. ranks
@@ -215,8 +217,13 @@ int prof_harvest(gk_ctx *c);
 void graph_reset(gk_ctx *c);
 void set_geometry(gk_ctx *c);
 int check_ctx(gk_ctx *c);
-int add_into(gk_ctx *c, double *x, const double *w);  // x += w (k_add, GK_KID_UPDATE)
-int fill_hash(gk_ctx *c, double *x, unsigned long long seed);  // k_fill_hash of the global index
+// ... and the range checks of the step and the update / v_err entries
+inline int check_step(const gk_ctx *c, int j) {
+    return j < 1 || j > c->m ? set_err(GK_ERR_ARG, "step j=%d outside 1..%d", j, c->m) : GK_OK;
+}
+inline int check_nout(const gk_ctx *c, int n_out) {
+    return n_out < 1 || n_out > c->m ? set_err(GK_ERR_ARG, "bad n_out %d", n_out) : GK_OK;
+}
 // The short-recurrence solvers keep their vectors in the Krylov columns and their
 // state on the device: any call that changes the operator data, the right-hand
 // side or x, or that starts a GMRES cycle (which overwrites the columns), ends the
@@ -236,6 +243,15 @@ template <class T>  // column k (0-based) of the MGS-R basis in the type T it is
 inline T *vcol(const gk_ctx *c, int k) { return reinterpret_cast<T *>(c->V) + (i64)k * c->ld; }
 inline double *cb_v1w(const gk_ctx *c) { return c->V + (i64)(c->m - 1) * c->ld; }
 inline double *cb_vjw(const gk_ctx *c) { return c->V + (i64)c->m * c->ld; }
+// The Krylov columns by non-temporal loads (GK_TUNE_PROJ_NT; auto: set_geometry's nt_auto)
+inline bool nt_cols(const gk_ctx *c) { return c->tune_nt > 0 || (c->tune_nt < 0 && c->nt_auto); }
+// H(1:j+1, j) of step j: its device slot, the mapped mirror the step's last kernel publishes
+// it to (the device's address of it) and the host's view of that mirror
+struct HCol { double *dev, *map; const volatile double *host; };
+inline HCol hcol_of(const gk_ctx *c, int j) {
+    const i64 off = (i64)(j - 1) * (c->m + 2);
+    return {c->hall + off, c->hallh_dev + off, c->hallh + off};
+}
 
 // gk_op.hip -- the operator A, the preconditioner M and their products.  acc: the reduction
 // fused into the launch that writes `out` (gk::ACC_*; ACC_DOT with vdot), its partials in
@@ -256,6 +272,26 @@ void mg_free(gk_ctx *c);
 int mg_apply(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part);
 int mg_transfer(gk_ctx *c, int what, int level, const double *a, const double *b, double *out);
 
+// gk_step.hip -- what every Arnoldi path launches, and the MGS-R cycle.  proj: one k_proj
+// launch on double columns (mode: gk::PJ_*; the float-column form stays inside the unit).
+int proj(gk_ctx *c, int mode, double *w, const double *va, const double *vb, const double *pin, int npin,
+         double *pout, double *hslot, double coef, i64 tail0 = 0, int hstore = 0);
+int scale(gk_ctx *c, double *out, const double *w, const double *pin, int npin, double *hslot,
+          double *hcopy = nullptr, const double *hsrc = nullptr, int ncopy = 0, bool pin_norm = false);
+int add_into(gk_ctx *c, double *x, const double *w);  // x += w (k_add, GK_KID_UPDATE)
+int fill_hash(gk_ctx *c, double *x, unsigned long long seed);  // k_fill_hash of the global index
+int finalize(gk_ctx *c, const double *pin, int npin, double *out, int take_sqrt);
+bool res_plan(gk_ctx *c, gk::ResPlan &p, bool hh = false);
+enum { RESF_CLOSE_HH = 1, RESF_UNIT_INIT = 2, RESF_PIN_LOCAL = 4 };  // res_step's flags
+int res_step(gk_ctx *c, int j, const gk::ResPlan &p, const double *pin, int npin, double *hs, double *hcopy,
+             int mode = gk::RES_MGS, double *w = nullptr, i64 unit_g = -1, int flags = 0);
+bool cb_plan_ctx(gk_ctx *c, gk::CbPlan &p);
+int d2h_sync(gk_ctx *c, double *host, const double *dev, int count);
+bool verr_ref_order(const gk_ctx *c);
+int ensure_gram(gk_ctx *c, int ncols);
+int gram(gk_ctx *c, const double *base, int ncols, std::vector<double> &G);
+int update_begin(gk_ctx *c, const double *y, int n_out);  // gk_update_x / gk_hh_update_x: checks, y to ydev
+
 // gk_comm.hip
 bool collective(const gk_ctx *c);
 void xs_set_timeout(gk_ctx *c, int ms);
@@ -265,6 +301,11 @@ int spin_until(gk_ctx *c, hipError_t (*query)(void *), void *obj, const char *wh
 hipError_t query_stream(void *s);
 hipError_t query_event(void *e);
 int sync_st(gk_ctx *c);
+// The tail of an entry that returns with its work done: the stream drained, then the profiling events
+inline int sync_harvest(gk_ctx *c) {
+    const int s = sync_st(c);
+    return s == GK_OK && c->prof ? prof_harvest(c) : s;
+}
 int allreduce(gk_ctx *c, double *buf, int count, bool vec = false);
 int bcast(gk_ctx *c, double *buf, int count, int root);
 int halo_lines(gk_ctx *c, const double *vec, int nl, double *lo, double *hi);

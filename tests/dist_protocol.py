@@ -1,5 +1,5 @@
 """Distributed restatement of the multi-GPU protocol of libgmres_hip
-(gmres_amd/csrc/gk_api.hip), in numpy over torch.distributed (gloo), for the
+(gmres_amd/csrc/gk_step.hip, gk_hh.hip, gk_comm.hip), in numpy over torch.distributed (gloo), for the
 CPU multi-process tests.  TEST INFRASTRUCTURE: it checks the decomposition
 (row-block slabs of grid lines, one-line halo exchange before every stencil,
 all-reduced partial dots, the Householder pivot owned by rank 0 and

@@ -286,7 +286,7 @@ def update_x_bound(x: np.ndarray, y: np.ndarray) -> float:
 def hh_start(c, P: np.ndarray, precondition: bool = False) -> None:
     """Open a Householder cycle on context c (cbpr2 on the left when preconditioned; collective
     on N ranks) and plant its slab P[k] of every reflector column k.  gk_set_x and
-    gk_vec_lincomb do not close a Householder cycle (cycle_hh, gk_api.hip), and every chain
+    gk_vec_lincomb do not close a Householder cycle (cycle_hh, gk_hh.hip), and every chain
     reads its reflectors from HBM."""
     import ctypes
 

@@ -71,7 +71,7 @@ def test_build_lists_the_unit():
     from gmres_amd import build as b
 
     assert [u[2] for u in b.HIP_UNITS_CGS] == ["gk_cgs.o"]
-    assert len(b.HIP_UNITS + b.HIP_UNITS_CB + b.HIP_UNITS_CGS) == 12
+    assert len(b.HIP_UNITS + b.HIP_UNITS_CB + b.HIP_UNITS_CGS) == 14
     remarks = ("gk_cgs.hip:36:1: remark: Function Name: _ZN2gk10k_cgs_dotsILi16ELb1EEEvPKdS2_xixPd\n"
                "gk_cgs.hip:36:1: remark:     ScratchSize [bytes/lane]: 8 [-Rpass-analysis=kernel-resource-usage]\n")
     assert b._scratch_kernels(remarks, "k_cgs_") == ["_ZN2gk10k_cgs_dotsILi16ELb1EEEvPKdS2_xixPd"]

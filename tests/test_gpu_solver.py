@@ -492,3 +492,99 @@ def test_sweep_driver_table():
         f = r.split()
         # columns: #, Vars, Iters, Restarts, gmres(n), Tol., L2, L_inf, Residual, ||I-V.t*V||, Time, Info
         assert int(f[1]) == 64 * 64 and float(f[8]) < 1e-15 and float(f[7]) < 1e-9
+
+
+# ------------------------------------------------------------ launch counts --
+T_RES, T_R2, T_SHARE, T_TMO, T_WONLY, T_HH_FUSE, T_GRAPH, T_PC, T_HH_NORM_ORDER = 8, 9, 10, 11, 13, 15, 19, 21, 25
+_WONLY = [(T_PC, -1), (T_RES, 1), (T_WONLY, 1), (T_R2, 12), (T_SHARE, 128), (T_TMO, 5000)]  # hh_data's forcing tunes
+
+
+def _mgs_launch(j, sten):  # launch path: the operator, 2 j k_proj (two passes of j projections), k_scale
+    return {"stencil": sten, "proj": 2 * j, "scale": 1}
+
+
+def _hh_launch(j, sten, norms):
+    # launch path: k_set_unit and the pivot / fix-up pair (one scope), + 2 k_norm2_seq with the reference-order
+    # norms; DOWN chain 1 + j k_proj (the leading dot, j reflections), UP chain j; the operator; k_scale
+    return {"other": 2 + norms, "proj": 2 * j + 1, "stencil": sten, "scale": 1}
+
+
+# route: (N, m, tunes, method, preconditioner, expected launches of the cycle start, of step j)
+STEP_LAUNCH_ROUTES = {
+    # MGS-R, one k_proj per projection: the start is b - A x (cbpr2: and its sweep), then k_scale
+    "mgs-launch-identity": (45, 12, [(T_RES, 0), (T_GRAPH, 0)], "mgs", "identity",
+                            {"stencil": 1, "scale": 1}, lambda j: _mgs_launch(j, 1)),
+    "mgs-launch-cbpr2": (45, 12, [(T_RES, 0), (T_GRAPH, 0)], "mgs", "cbpr2",
+                         {"stencil": 2, "scale": 1}, lambda j: _mgs_launch(j, 2)),
+    # MGS-R resident: the operator and one k_mgs_* launch, whatever j is
+    "mgs-resident": (45, 12, [(T_RES, 1)], "mgs", "identity",
+                     {"stencil": 1, "scale": 1}, lambda j: {"stencil": 1, "res": 1}),
+    # Householder: the start is b - A x, the pivot / fix-up pair (one scope), k_scale
+    "hh-launch-none": (45, 12, [(T_RES, 0)], "hh", "none",
+                       {"stencil": 1, "other": 1, "scale": 1}, lambda j: _hh_launch(j, 1, 0)),
+    "hh-launch-left": (45, 12, [(T_RES, 0)], "hh", "left",
+                       {"stencil": 2, "other": 1, "scale": 1}, lambda j: _hh_launch(j, 2, 0)),
+    # ... with GK_TUNE_HH_NORM_ORDER 1: a k_norm2_seq before the pivot and one before k_scale
+    "hh-launch-norm-order": (45, 12, [(T_RES, 0), (T_HH_NORM_ORDER, 1)], "hh", "none",
+                             {"stencil": 1, "other": 3, "scale": 1}, lambda j: _hh_launch(j, 1, 2)),
+    # ... and on the resident chains (DOWN, UP: 2 launches), which the reference-order norms leave unfused
+    "hh-resident-norm-order": (45, 12, [(T_RES, 1), (T_HH_NORM_ORDER, 1)], "hh", "none",
+                               {"stencil": 1, "other": 3, "scale": 1},
+                               lambda j: {"other": 4, "res": 2, "stencil": 1, "scale": 1}),
+    # w-only chains, fused: DOWN builds e_j, UP closes the step; what is left is the operator and k_hh_pivot
+    "hh-wonly-fused": (181, 16, _WONLY + [(T_HH_FUSE, 1)], "hh", "none",
+                       {"stencil": 1, "other": 1, "scale": 1}, lambda j: {"other": 1, "res": 2, "stencil": 1}),
+    # ... unfused: k_set_unit, the two chains, the operator, the pivot / fix-up pair, k_scale
+    "hh-wonly-unfused": (181, 16, _WONLY + [(T_HH_FUSE, 0)], "hh", "none",
+                         {"stencil": 1, "other": 1, "scale": 1},
+                         lambda j: {"other": 2, "res": 2, "stencil": 1, "scale": 1}),
+}
+
+
+@pytest.mark.parametrize("route", sorted(STEP_LAUNCH_ROUTES))
+def test_step_launch_counts(route):
+    """Launches per kernel id (gk_profile_read) of one cycle start and of steps j = 1, 2 and 5 on
+    every host route of the MGS-R and the Householder step: the host path launches what it
+    launched, in the scopes it launched it in.  One rank: no collective opens a scope.  The
+    element values of these routes are held by test_gpu_step_known_answer.py,
+    test_gpu_hh_step_known_answer.py, test_gpu_hh_right.py and test_gpu_resident.py."""
+    import ctypes
+
+    import gmres_amd as ga
+    from gmres_amd import _native as nat
+
+    N, m, tunes, method, prec, want_start, want_step = STEP_LAUNCH_ROUTES[route]
+    L = nat.hip()
+    mode = {"none": nat.GK_HH_PREC_NONE, "left": nat.GK_HH_PREC_LEFT}.get(prec, 0)
+
+    def launches(c):
+        got = {k: n for k, (_, n) in c.profile_read().items() if n}
+        c.profile_reset()
+        return got
+
+    with ga.Context(N, m) as c:
+        for k, v in tunes:
+            c.tune(k, v)
+        c.set_precond("cbpr2" if prec in ("cbpr2", "left") else "identity", (8.2, 0.2))
+        c.set_rhs_ones()
+        if method == "hh" and T_WONLY in dict(tunes):
+            assert c.res_info(hh=True)["variant"] == "w-only"
+        c.profile(True)
+        c.profile_reset()
+        if method == "mgs":
+            c.mgs_cycle_start()
+        else:
+            g1 = ctypes.c_double()
+            nat.check(L.gk_hh_cycle_start(c.handle, mode, ctypes.byref(g1)), "gk_hh_cycle_start")
+        got = {0: launches(c)}
+        h = np.zeros(m + 2)
+        for j in range(1, 6):
+            if method == "mgs":
+                c.mgs_step(j)
+            else:
+                nat.check(L.gk_hh_step(c.handle, j, mode, h.ctypes.data_as(nat._dp)), "gk_hh_step")
+            got[j] = launches(c)
+        print(f"{route}: " + ", ".join(f"j={j}: {got[j]}" for j in (0, 1, 2, 5)))
+        assert got[0] == want_start
+        for j in (1, 2, 5):
+            assert got[j] == want_step(j), (j, got[j])

@@ -110,10 +110,10 @@ def test_build_refuses_chebyshev_scratch_spills():
                "gk_cheb.hip:46:1: remark:     ScratchSize [bytes/lane]: 16 [-Rpass-analysis=kernel-resource-usage]\n"
                "gk_cheb.hip:46:1: remark: Function Name: _ZN2gk12k_cheb_fusedILi4ELb1ELb1ELi1ELb0EEEvNS_6CFArgsE\n"
                "gk_cheb.hip:46:1: remark:     ScratchSize [bytes/lane]: 0 [-Rpass-analysis=kernel-resource-usage]\n"
-               "gk_api.hip:9:1: remark: Function Name: _ZN2gk6k_projILi0ELb1ELi2EEEvPdPKdS3_\n"
-               "gk_api.hip:9:1: remark:     ScratchSize [bytes/lane]: 32 [-Rpass-analysis=kernel-resource-usage]\n")
+               "gk_step.hip:9:1: remark: Function Name: _ZN2gk6k_projILi0ELb1ELi2EEEvPdPKdS3_\n"
+               "gk_step.hip:9:1: remark:     ScratchSize [bytes/lane]: 32 [-Rpass-analysis=kernel-resource-usage]\n")
     assert b._scratch_kernels(remarks, "k_cheb_fused") == ["_ZN2gk12k_cheb_fusedILi8ELb1ELb1ELi1ELb0EEEvNS_6CFArgsE"]
-    assert [u[2] for u in b.HIP_UNITS] == (["gk_api.o", "gk_op.o"]
+    assert [u[2] for u in b.HIP_UNITS] == (["gk_api.o", "gk_step.o", "gk_hh.o", "gk_op.o"]
                                            + [f"gk_cheb{p}.o" for p in range(b.GK_CF_PARTS)]
                                            + ["gk_blk.o", "gk_resident.o", "gk_comm.o", "gk_sr_api.o"])
     # the blocked-projection step's kernels (gk_blk.hip) are held to the same rule
