@@ -20,6 +20,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from tests import mg_data
 from tests.right_gmres_host import PARAMS, _back_solve, _givens
 
 # the issue's table: (N, m, preconditioner, degree, side, tol, max_cycles)
@@ -64,13 +65,16 @@ class CbResult:
 def gmres_cb_host(orc, N, m, prec="cbpr2", degree=8, side="left", tol=1e-8, params=PARAMS, max_cycles=1000,
                   basis="f32", guard=True, threads=1, b=None) -> CbResult:
     assert side in ("left", "right") and basis in ("f32", "f64")
-    kind = {"identity": orc.PREC_IDENTITY, "cbpr2": orc.PREC_CBPR2, "cheb": orc.PREC_CHEB}[prec]
+    kind = "mg" if prec == "mg" else {"identity": orc.PREC_IDENTITY, "cbpr2": orc.PREC_CBPR2, "cheb": orc.PREC_CHEB}[prec]
     store = round32 if basis == "f32" else (lambda v: v)
     orc.set_threads(threads)
     try:
         n = N * N
         b = orc.rhs_ones(N) if b is None else np.ascontiguousarray(b, dtype=np.float64)
-        minv = lambda r: orc.precond(kind, r, N, params=params, degree=degree)  # noqa: E731
+        if kind == "mg":  # the aggregation multigrid V-cycle's restatement (tests/mg_data.py)
+            minv = lambda r: mg_data.mg(orc, r, N, params, degree)  # noqa: E731
+        else:
+            minv = lambda r: orc.precond(kind, r, N, params=params, degree=degree)  # noqa: E731
         beta0 = orc.norm2(b)
         x = np.zeros(n)
         final_err = np.zeros(m)

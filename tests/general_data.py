@@ -12,6 +12,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from tests import mg_data
+
 EPS = 2.0 ** -52
 MARGIN = 64.0  # over the first-order rounding error of one dot, eps ||w|| ||v||
 
@@ -146,27 +148,37 @@ def check_step(h, v_new, V, w0, ref=None, what="", bounds=None, plan=None):
 # ------------------------------------- preconditioned steps, both basis formats ---
 
 PARAMS = (8.2, 0.2)
-# (id, side, preconditioner, degree, tunes by name, N, m): the step's first dot comes from the
-# operator launch's epilogue; steps j = 1, 2, m on the launch path and on one resident plan
-# (test_gpu_step_known_answer.py on FP64 columns, test_gpu_cb_step_known_answer.py on FP32)
+MG_PARAMS, MG_DEGREE = mg_data.DEFAULT_PARAMS, mg_data.DEFAULT_DEGREE  # (8.0, 1.0), 2
+# (id, side, preconditioner, degree, tunes by name, N, m, params): the step's first dot comes
+# from the operator launch's epilogue; steps j = 1, 2, m on the launch path and on one resident
+# plan (test_gpu_step_known_answer.py on FP64 columns, test_gpu_cb_step_known_answer.py on FP32,
+# test_gpu_cgs2_step_known_answer.py in front of the CGS2 chain).  The multigrid rows: on the
+# left the cycle's closing add carries the dot (k_mg_add<ACC_DOT>); 48 has three levels,
+# 130 a coarse side of 65 (odd, and a wave seam at fine column 128), 256 six levels.
 PREC_STEP_CASES = (
-    [(f"left-cbpr2-{N}", "left", "cbpr2", 1, (), N, 6) for N in (45, 130)]
-    + [(f"left-cheb{d}-sten{s}-{N}", "left", "cheb", d, (("GK_TUNE_CHEB_STEN", s),), N, 6)
+    [(f"left-cbpr2-{N}", "left", "cbpr2", 1, (), N, 6, PARAMS) for N in (45, 130)]
+    + [(f"left-cheb{d}-sten{s}-{N}", "left", "cheb", d, (("GK_TUNE_CHEB_STEN", s),), N, 6, PARAMS)
        for d, N in ((4, 130), (8, 130), (4, 256), (8, 256), (11, 130), (4, 45)) for s in (1, 0)]
-    + [(f"right-cbpr2-fused{f}-{N}", "right", "cbpr2", 1, (("GK_TUNE_RIGHT_FUSED", f),), N, 6)
+    + [(f"right-cbpr2-fused{f}-{N}", "right", "cbpr2", 1, (("GK_TUNE_RIGHT_FUSED", f),), N, 6, PARAMS)
        for N in (65, 130) for f in (1, 0)]
-    + [("right-cheb3-130", "right", "cheb", 3, (), 130, 6)])
+    + [("right-cheb3-130", "right", "cheb", 3, (), 130, 6, PARAMS)]
+    + [(f"left-mg-{N}", "left", "mg", MG_DEGREE, (), N, 6, MG_PARAMS) for N in (48, 130, 256)]
+    + [(f"right-mg-{N}", "right", "mg", MG_DEGREE, (), N, 6, MG_PARAMS) for N in (48, 130)])
 
 
-def op_w0(oracle, v: np.ndarray, N: int, side: str = "left", prec: str = "identity", degree: int = 1) -> np.ndarray:
+def op_w0(oracle, v: np.ndarray, N: int, side: str = "left", prec: str = "identity", degree: int = 1,
+          params=PARAMS) -> np.ndarray:
     """The operator stage of a step on the oracle (bit-exact with the device operators,
-    test_gpu_kernels.py / test_gpu_right_precond.py): M^-1 A v on the left, A M^-1 v on the right."""
+    test_gpu_kernels.py / test_gpu_right_precond.py; "mg": the restated V-cycle, test_gpu_mg.py):
+    M^-1 A v on the left, A M^-1 v on the right."""
     if prec == "identity":
         return oracle.stvec(v, N)
+    if prec == "mg":
+        return mg_data.op_mg(oracle, v, N, side, params, degree)
     kind = {"cbpr2": oracle.PREC_CBPR2, "cheb": oracle.PREC_CHEB}[prec]
     if side == "right":
-        return oracle.stvec(oracle.precond(kind, v, N, params=PARAMS, degree=degree), N)
-    return oracle.precond(kind, oracle.stvec(v, N), N, params=PARAMS, degree=degree)
+        return oracle.stvec(oracle.precond(kind, v, N, params=params, degree=degree), N)
+    return oracle.precond(kind, oracle.stvec(v, N), N, params=params, degree=degree)
 
 
 def stencil_any(v: np.ndarray, N: int) -> np.ndarray:

@@ -97,26 +97,82 @@ def _cycle(oracle, r, sides, l, params, degree):
     return z + cheb(t)
 
 
-def pcg(oracle, N: int, params=DEFAULT_PARAMS, degree: int = DEFAULT_DEGREE, tol: float = 1e-8, max_iter: int = 200):
-    """Preconditioned CG with the restated cycle, b = A 1, x0 = 0, to ||r|| / ||b|| < tol:
-    (iterations, final relative residual)."""
-    b = oracle.rhs_ones(N)
+def op_mg(oracle, v: np.ndarray, N: int, side: str = "left", params=DEFAULT_PARAMS,
+          degree: int = DEFAULT_DEGREE) -> np.ndarray:
+    """The operator stage of an MG-preconditioned Arnoldi step: M^-1 A v on the left,
+    A M^-1 v on the right."""
+    if side == "right":
+        return oracle.stvec(mg(oracle, v, N, params, degree), N)
+    return mg(oracle, oracle.stvec(v, N), N, params, degree)
+
+
+def pcg(oracle, N: int, params=DEFAULT_PARAMS, degree: int = DEFAULT_DEGREE, tol: float = 1e-8, max_iter: int = 200,
+        b=None, full: bool = False):
+    """Preconditioned CG with the restated cycle in the oracle's operation order for pcg_omp,
+    x0 = 0, every reduction through oracle.dot / oracle.norm2 (oracle.set_threads changes their
+    summation order).  b = None: b = A 1, stopped on ||r|| / ||b|| < tol, returns
+    (iterations, final relative residual).  full = True: also the history of ||r|| (absolute,
+    one entry per iteration run) and x -- (iterations, relative residual, history, x); with
+    tol = 0 that is exactly max_iter iterations."""
+    b = oracle.rhs_ones(N) if b is None else np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
     x = np.zeros_like(b)
     r = b.copy()
     z = mg(oracle, r, N, params, degree)
     p = z.copy()
-    rz = float(r @ z)
-    bn = float(np.sqrt(b @ b))
+    rz = oracle.dot(r, z)
+    bn = oracle.norm2(b)
+    hist = []
+    it, rel = 0, 1.0
     for it in range(1, max_iter + 1):
         ap = oracle.stvec(p, N)
-        alpha = rz / float(p @ ap)
-        x += alpha * p
-        r -= alpha * ap
-        rel = float(np.sqrt(r @ r)) / bn
+        alpha = rz / oracle.dot(ap, p)
+        x = x + alpha * p
+        r = r - alpha * ap
+        res = oracle.norm2(r)
+        hist.append(res)
+        rel = res / bn
         if rel < tol:
-            return it, rel
+            break
         z = mg(oracle, r, N, params, degree)
-        rz_new = float(r @ z)
+        rz_new = oracle.dot(r, z)
         p = z + (rz_new / rz) * p
         rz = rz_new
-    return max_iter, rel
+    return (it, rel, np.array(hist), x) if full else (it, rel)
+
+
+def pbicgstab(oracle, b: np.ndarray, N: int, max_iter: int, params=DEFAULT_PARAMS, degree: int = DEFAULT_DEGREE):
+    """Preconditioned BiCGSTAB with M^-1 = mg in the oracle's operation order for pbicgstab_omp
+    (x0 = 0, r0 = p = r = b; z1 = M^-1 p, alpha = <r, r0> / <A z1, r0>; s = r - alpha A z1;
+    z2 = M^-1 s, omega = <A z2, s> / <A z2, A z2>; x = x + alpha z1 + omega z2; r = s - omega A z2;
+    beta = (<r, r0> / <r_old, r0>) (alpha / omega); p = r + beta (p - omega A z1)), a fixed
+    max_iter iterations: (history of ||r||, x).  A zero denominator ends the run at the last
+    finite iteration."""
+    b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+    x = np.zeros_like(b)
+    r = b.copy()
+    r0 = r.copy()
+    p = r.copy()
+    hist = []
+    for _ in range(max_iter):
+        z1 = mg(oracle, p, N, params, degree)
+        ap = oracle.stvec(z1, N)
+        rr0 = oracle.dot(r, r0)
+        ap_r0 = oracle.dot(ap, r0)
+        if ap_r0 == 0.0 or rr0 == 0.0:
+            break
+        alpha = rr0 / ap_r0
+        s = r - alpha * ap
+        z2 = mg(oracle, s, N, params, degree)
+        as_ = oracle.stvec(z2, N)
+        as_as = oracle.dot(as_, as_)
+        if as_as == 0.0:
+            break
+        omega = oracle.dot(as_, s) / as_as
+        if omega == 0.0:
+            break
+        x = (x + alpha * z1) + omega * z2
+        r = s - omega * as_
+        hist.append(oracle.norm2(r))
+        beta = (oracle.dot(r, r0) / rr0) * (alpha / omega)
+        p = r + beta * (p - omega * ap)
+    return np.array(hist), x

@@ -21,6 +21,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from tests import mg_data
+
 # the six cases of the issue's table: (N, m, preconditioner, degree, max_cycles)
 CASES = [
     (32, 10, "cbpr2", 0, 1000),
@@ -85,7 +87,7 @@ def _back_solve(H, g, n_out, m):
 def gmres_mgsr_host(orc, N, m, prec="cbpr2", degree=8, side="left", tol=TOL, params=PARAMS,
                     max_cycles=1000, b=None, threads=1) -> HostResult:
     assert side in ("left", "right")
-    kind = {"identity": orc.PREC_IDENTITY, "cbpr2": orc.PREC_CBPR2, "cheb": orc.PREC_CHEB}[prec]
+    kind = "mg" if prec == "mg" else {"identity": orc.PREC_IDENTITY, "cbpr2": orc.PREC_CBPR2, "cheb": orc.PREC_CHEB}[prec]
     orc.set_threads(threads)
     try:
         return _mgsr_host(orc, N, m, kind, degree, side, tol, params, max_cycles, b)
@@ -96,7 +98,10 @@ def gmres_mgsr_host(orc, N, m, prec="cbpr2", degree=8, side="left", tol=TOL, par
 def _mgsr_host(orc, N, m, kind, degree, side, tol, params, max_cycles, b) -> HostResult:
     n = N * N
     b = orc.rhs_ones(N) if b is None else np.ascontiguousarray(b, dtype=np.float64)
-    minv = lambda r: orc.precond(kind, r, N, params=params, degree=degree)  # noqa: E731
+    if kind == "mg":  # the aggregation multigrid V-cycle's restatement (tests/mg_data.py)
+        minv = lambda r: mg_data.mg(orc, r, N, params, degree)  # noqa: E731
+    else:
+        minv = lambda r: orc.precond(kind, r, N, params=params, degree=degree)  # noqa: E731
     beta0 = orc.norm2(b)
     x = np.zeros(n)
     final_err = np.zeros(m)

@@ -15,7 +15,7 @@ against gk_cb_plan_query (pure host)."""
 import numpy as np
 import pytest
 
-from tests.general_data import (CB_LAUNCH_SHAPES, PREC_STEP_CASES, CB_RES_JS, CB_RES_M, CB_RES_PLANS, assert_asymmetric,
+from tests.general_data import (CB_LAUNCH_SHAPES, MG_PARAMS, PARAMS, PREC_STEP_CASES, CB_RES_JS, CB_RES_M, CB_RES_PLANS, assert_asymmetric,
                                 cb_column_excess, cb_planted, cb_step_ld, locate_cb, op_w0, planted_basis,
                                 planted_basis_f32, step_bounds, ulp32)
 
@@ -92,7 +92,9 @@ def _ratios(h, stored, V, w0, ref):
 def _pin_cases():
     out = [(N, m, j, "left", "identity", 1) for N, m in CB_LAUNCH_SHAPES for j in (1, 2, m)]
     out += [(N, CB_RES_M, j, "left", "identity", 1) for N in sorted({p[0] for p in CB_RES_PLANS}) for j in CB_RES_JS]
-    out += [(N, m, j, side, prec, deg) for _, side, prec, deg, _, N, m in PREC_STEP_CASES for j in (1, 2, m)]
+    for _, side, prec, deg, _, N, m, params in PREC_STEP_CASES:
+        assert params == (MG_PARAMS if prec == "mg" else PARAMS)  # the test below derives them from prec
+        out += [(N, m, j, side, prec, deg) for j in (1, 2, m)]
     return sorted(set(out))
 
 
@@ -120,7 +122,7 @@ def test_ulp32():
 @pytest.mark.parametrize("N,m,j,side,prec,deg", _pin_cases())
 def test_cb_step_bounds_pass_a_reordered_step(oracle, N, m, j, side, prec, deg):
     V = cb_planted(N, m)[:j]
-    w0 = op_w0(oracle, V[j - 1], N, side, prec, deg)
+    w0 = op_w0(oracle, V[j - 1], N, side, prec, deg, MG_PARAMS if prec == "mg" else PARAMS)
     ref = cb_step_ld(V, w0)
     assert abs(float(np.sqrt(np.dot(ref[1], ref[1]))) - 1.0) < 1e-14
     rh, rv, n_off = _ratios(*_step_f64(V, w0), V, w0, ref)

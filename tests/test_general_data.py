@@ -2,13 +2,15 @@
 general_rhs has none of the square's symmetries while b = A*1 and its Krylov vectors have
 all of them, and the single-step bound of test_gpu_step_known_answer.py -- 64 eps ||w|| ||v||
 per Hessenberg entry, 64 eps max|v_ref| per element of the new column -- passes a correct
-float64 step with another summation tree by a factor of 8 or more and fails each seeded fault.
+float64 step with another summation tree by a factor of 8 or more and fails each seeded fault
+(with the multigrid cycle as the operator, which cancels w0 to a tenth: by a factor of 2).
 """
 import numpy as np
 import pytest
 
-from tests.general_data import (asymmetry, assert_asymmetric, blocked_step, general_rhs, mgs_step_ld,
-                                planted_basis, step_bounds)
+from tests import mg_data
+from tests.general_data import (MG_DEGREE, MG_PARAMS, PREC_STEP_CASES, asymmetry, assert_asymmetric, blocked_step,
+                                general_rhs, mgs_step_ld, planted_basis, step_bounds)
 
 
 def test_general_rhs_is_asymmetric_and_rhs_ones_is_not(oracle):
@@ -84,6 +86,34 @@ def test_step_bound_passes_reordering_and_fails_seeded_faults(oracle, N, j):
     for fault in ("dot_tail", "axpy1", "axpy2", "one_pass"):
         fh, fv = _ratios(*_step_f64(V, w0, fault), V, w0, ref)
         print(f"N={N} j={j}: {fault}: h dev/bound {fh:.3e}, column dev/bound {fv:.3e}")
+        assert max(fh, fv) > 10.0, fault
+
+
+MG_PIN_CASES = ([(c[1], c[5], c[6], j) for c in PREC_STEP_CASES if c[2] == "mg" for j in (1, 2, c[6])]
+                + [("left", 1450, 2, j) for j in (1, 2)])
+
+
+@pytest.mark.parametrize("side,N,m,j", MG_PIN_CASES, ids=[f"{s}-{N}-j{j}" for s, N, m, j in MG_PIN_CASES])
+def test_step_bound_with_multigrid_operator(oracle, side, N, m, j):
+    """The multigrid rows of PREC_STEP_CASES and the N = 1450 step of test_gpu_mg.py, on the
+    columns the GPU tests plant (seed 5000 + 7 N + m): w0 = M^-1 A v (right: A M^-1 v) from the
+    restated cycle.  M^-1 approximates A^-1, so the step cancels w0 = v_j + (a remainder of
+    about a tenth of it) down to h(j+1) / ||w0|| ~ 0.1 and the new column's rounding error,
+    eps ||w0|| / h(j+1) per element, uses more of its bound than on the identity: the reordered
+    float64 step stays below 1/2 of both bounds (measured: h <= 0.004, column <= 0.19, the
+    level the Chebyshev(8) rows reach), and every seeded fault still exceeds 10 (>= 2.9e3)."""
+    V = planted_basis(N, m, seed=5000 + 7 * N + m)[:j]
+    for k in range(j):
+        assert_asymmetric(V[k], N)
+    w0 = mg_data.op_mg(oracle, V[j - 1], N, side, MG_PARAMS, MG_DEGREE)
+    ref = mgs_step_ld(V, w0)
+    print(f"mg {side} N={N} j={j}: h(j+1) / ||w0|| {ref[0][j] / np.linalg.norm(w0):.3f}")
+    rh, rv = _ratios(*_step_f64(V, w0), V, w0, ref)
+    print(f"mg {side} N={N} j={j}: reordered float64 step, h dev/bound {rh:.4f}, column dev/bound {rv:.4f}")
+    assert rh <= 0.5 and rv <= 0.5
+    for fault in ("dot_tail", "axpy1", "axpy2", "one_pass"):
+        fh, fv = _ratios(*_step_f64(V, w0, fault), V, w0, ref)
+        print(f"mg {side} N={N} j={j}: {fault}: h dev/bound {fh:.3e}, column dev/bound {fv:.3e}")
         assert max(fh, fv) > 10.0, fault
 
 

@@ -39,12 +39,12 @@ T_PROJ_NT, T_PROJ_BLOCKS, T_RES, T_SHARE, T_TMO, T_VERR_ORDER, T_GRAPH = 0, 1, 8
 _refs: dict = {}
 
 
-def _ref(oracle, N, m, j, side="left", prec="identity", degree=1):
+def _ref(oracle, N, m, j, side="left", prec="identity", degree=1, params=PARAMS):
     """(V[:j], w0, (h_ref, v_ref in long double)) of step j on the planted float columns."""
-    key = (N, m, j, side, prec, degree)
+    key = (N, m, j, side, prec, degree, params)
     if key not in _refs:
         V = cb_planted(N, m)[:j]
-        w0 = op_w0(oracle, V[j - 1], N, side, prec, degree)
+        w0 = op_w0(oracle, V[j - 1], N, side, prec, degree, params)
         _refs[key] = (V, w0, cb_step_ld(V, w0))
     return _refs[key]
 
@@ -55,7 +55,7 @@ def _tunes(named):
     return [(getattr(nat, k) if isinstance(k, str) else k, v) for k, v in named]
 
 
-def _open(N, m, tunes, side="left", prec="identity", degree=1, ncols=None):
+def _open(N, m, tunes, side="left", prec="identity", degree=1, ncols=None, params=PARAMS):
     """An FP32-basis context with its tuning applied and an MGS-R cycle open; columns
     0..ncols-1 (default m) planted through gk_set_basis."""
     import gmres_amd as ga
@@ -64,7 +64,7 @@ def _open(N, m, tunes, side="left", prec="identity", degree=1, ncols=None):
     try:
         for k, v in _tunes(tunes):
             c.tune(k, v)
-        c.set_precond(prec, PARAMS, degree, side=side)
+        c.set_precond(prec, params, degree, side=side)
         c.set_basis("f32")
         c.set_rhs_ones()
         c.mgs_cycle_start()
@@ -194,12 +194,12 @@ def test_preconditioned_step(oracle, case, route):
     route on two workgroups (130^2: 17 + 16 chunks)."""
     from gmres_amd import _native as nat
 
-    _, side, prec, degree, named, N, m = case
+    _, side, prec, degree, named, N, m, params = case
     if route == "launch":
         tunes = [(T_RES, 0)] + list(named)
     else:
         tunes = [(T_RES, 1), (T_SHARE, _share(2)[0]), (T_TMO, 5000)] + list(named)
-    c = _open(N, m, tunes, side=side, prec=prec, degree=degree)
+    c = _open(N, m, tunes, side=side, prec=prec, degree=degree, params=params)
     with c:
         plan = c.res_info()
         if route == "launch":
@@ -210,7 +210,7 @@ def test_preconditioned_step(oracle, case, route):
                 assert plan["r2e"] == 17 and plan["l2e"] == 0, plan
         c.profile(True)
         c.profile_reset()
-        _check(oracle, c, N, m, [1, 2, m], f"{case[0]} {route}", op=(side, prec, degree))
+        _check(oracle, c, N, m, [1, 2, m], f"{case[0]} {route}", op=(side, prec, degree, params))
         prof = c.profile_read()
     if route == "launch":
         assert prof["res"][1] == 0, prof

@@ -59,7 +59,7 @@ def _batch_env(kb):
                 os.environ["GK_CGS_KB"] = old
 
 
-def _open(N, m, tunes, side="left", prec=("identity", 1), kb=None):
+def _open(N, m, tunes, side="left", prec=("identity", 1), kb=None, params=PARAMS):
     """A CGS2 context with its tuning applied and an MGS-R cycle open; every column planted.
     kb: the dots kernel's batch, which gk_create reads from GK_CGS_KB."""
     import gmres_amd as ga
@@ -69,7 +69,7 @@ def _open(N, m, tunes, side="left", prec=("identity", 1), kb=None):
     try:
         for k, v in tunes:
             c.tune(k, v)
-        c.set_precond(prec[0], PARAMS, prec[1], side=side)
+        c.set_precond(prec[0], params, prec[1], side=side)
         c.set_orth("cgs2")
         c.set_rhs_ones()
         c.mgs_cycle_start()
@@ -168,12 +168,12 @@ def test_cgs2_preconditioned_step(oracle, case):
     """Every preconditioner route on either side in front of the CGS2 chain (the operator stage
     without its fused first dot, except Chebyshev on the left, whose slab stays unconsumed)."""
     nat = _nat()
-    _, side, kind, degree, named, N, m = case
+    _, side, kind, degree, named, N, m, params = case
     tunes = [(getattr(nat, k), v) for k, v in named]
-    c = _open(N, m, tunes, side=side, prec=(kind, degree))
+    c = _open(N, m, tunes, side=side, prec=(kind, degree), params=params)
     with c:
         assert c.res_info()["variant"] is None
-        _check(oracle, c, N, m, [1, 2, m], f"cgs2 {case[0]}", op=(side, kind, degree))
+        _check(oracle, c, N, m, [1, 2, m], f"cgs2 {case[0]}", op=(side, kind, degree, params))
 
 
 def test_batch_knob_rejects_other_sizes():

@@ -67,7 +67,7 @@ def _V(N, m):
 
 def _ref(oracle, N, m, j, op=None):
     """(V[:j], w0, (h_ref, v_ref)) of step j on the planted columns; once per case.
-    op = (side, kind, degree): the preconditioned operator instead of A."""
+    op = (side, kind, degree, params): the preconditioned operator instead of A."""
     key = (N, m, j) if op is None else (N, m, j, op)
     if key not in _refs:
         V = _V(N, m)[:j]
@@ -84,16 +84,16 @@ def _blk_ref(N, m, j, S, V, w0):
     return _refs[key]
 
 
-def _open(N, m, tunes, side="left", prec=("identity", 1), **kw):
+def _open(N, m, tunes, side="left", prec=("identity", 1), params=PARAMS, **kw):
     """A context with its tuning applied and an MGS-R cycle open on the identity
-    preconditioner (or prec = (kind, degree)); every column 0..m-1 planted."""
+    preconditioner (or prec = (kind, degree) on `params`); every column 0..m-1 planted."""
     import gmres_amd as ga
 
     c = ga.Context(N, m, **kw)
     try:
         for k, v in tunes:
             c.tune(k, v)
-        c.set_precond(prec[0], PARAMS, prec[1], side=side)
+        c.set_precond(prec[0], params, prec[1], side=side)
         c.set_rhs_ones()
         c.mgs_cycle_start()
         V = _V(N, m)
@@ -285,13 +285,13 @@ def test_preconditioned_step(oracle, case, route):
     from gmres_amd import _native as nat
     from tests.test_gpu_wres_carry import _workgroups_share
 
-    _, side, kind, degree, named, N, m = case
+    _, side, kind, degree, named, N, m, params = case
     tunes = [(getattr(nat, k), v) for k, v in named]
     if route == "launch":
         tunes += [(T_RES, 0)]
     else:
         tunes += _res_tunes(12, _workgroups_share(2), 1, 0)
-    c = _open(N, m, tunes, side=side, prec=(kind, degree))
+    c = _open(N, m, tunes, side=side, prec=(kind, degree), params=params)
     with c:
         plan = c.res_info()
         print(f"{case[0]} {route}: {plan}")
@@ -301,7 +301,7 @@ def test_preconditioned_step(oracle, case, route):
             assert plan["variant"] == ("w-only" if N >= 130 else "prefetch") and plan["G"] == 2, plan
         c.profile(True)
         c.profile_reset()
-        _check(oracle, c, N, m, [1, 2, m], f"{case[0]} {route}", op=(side, kind, degree))
+        _check(oracle, c, N, m, [1, 2, m], f"{case[0]} {route}", op=(side, kind, degree, params))
         prof = c.profile_read()
     if route == "launch":
         assert prof["res"][1] == 0, prof
