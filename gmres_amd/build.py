@@ -60,8 +60,8 @@ HIP_UNITS_MG = [_unit("gk_mg")]
 HIP_UNITS_ALL = HIP_UNITS + HIP_UNITS_CB + HIP_UNITS_CGS + HIP_UNITS_MG
 HIP_SOURCES = sorted({u[0] for u in HIP_UNITS_ALL})
 HIP_HEADERS = [os.path.join(CSRC, h) for h in ("gk_common.hpp", "gk_kernels.hpp", "gk_step_kernels.hpp",
-                                                "gk_hh_kernels.hpp", "gk_stencil.hpp", "gk_cheb.hpp", "gk_res.hpp",
-                                                "gk_blk.hpp", "gk_sr.hpp", "gk_host.hpp", "gk_resident.hpp",
+                                                "gk_hh_kernels.hpp", "gk_march.hpp", "gk_stencil.hpp", "gk_cheb.hpp",
+                                                "gk_res.hpp", "gk_blk.hpp", "gk_sr.hpp", "gk_host.hpp", "gk_resident.hpp",
                                                 "gk_cb.hpp", "gk_cgs.hpp", "gk_mg.hpp")]
 HIP_DEPS = HIP_SOURCES + HIP_HEADERS + [os.path.join(ROOT, "include", "gmres_hip.h")]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall"]

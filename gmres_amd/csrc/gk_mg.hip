@@ -10,6 +10,7 @@
 // writes z, 18; the closing add reads two vectors and writes one, 24 (+ 8 for a dot partner).
 #include <cmath>
 
+#include "gk_march.hpp"
 #include "gk_mg.hpp"
 
 namespace gk {
@@ -42,13 +43,12 @@ int mg_coarse_degree(int NL, double *lo, double *hi) {
 }
 
 // -------------------------------------------------------------- restrict ---
-// k_stencil's line march on the fine grid, two points per lane (N even: a lane's pair is
-// one coarse column I = i0 / 2), an even number of lines from an even j0 (a line pair is
-// one coarse line J = j / 2).  RESID: lines j-1, j, j+1 of z in registers, W/E from the
-// adjacent lanes by __shfl (lanes 0 and 63 read their outer neighbour through L1), and
-// f = r - A z in OP_RESID's expression, never stored.  Else f = x as stored.  One coarse
-// double per lane and line pair: rc(I,J) = ((f(2I,2J) + f(2I+1,2J)) + f(2I,2J+1)) + f(2I+1,2J+1).
-// Lanes past the line's end (levels narrower than the workgroup) are masked like k_stencil's.
+// The line march of gk_march.hpp on the fine grid, two points per lane (N even: a lane's
+// pair is one coarse column I = i0 / 2), an even number of lines from an even j0 (a line
+// pair is one coarse line J = j / 2).  RESID: the march on z (we_load) with f = r - A z in
+// OP_RESID's expression, never stored.  Else f = x as stored.  One coarse double per lane
+// and line pair: rc(I,J) = ((f(2I,2J) + f(2I+1,2J)) + f(2I,2J+1)) + f(2I+1,2J+1).  Levels
+// narrower than the workgroup leave lanes past the line's end.
 struct MgrArgs {
     const double *x;  // RESID: z ; else f
     const double *r;  // RESID: the right-hand side of the residual
@@ -59,56 +59,42 @@ struct MgrArgs {
 template <bool RESID>
 __global__ __launch_bounds__(TPB) void k_mg_restrict(MgrArgs a) {
     const int N = a.N, Nc = N >> 1;
-    const int lane = threadIdx.x & 63;
-    const i64 i0 = (i64)blockIdx.x * (TPB * 2) + (i64)2 * threadIdx.x;
-    const bool act = i0 < N;
-    const int j0 = blockIdx.y * a.JT;
-    const int j1 = min(j0 + a.JT, N);  // even: N and JT are
-    if (j0 >= N) return;
+    const March m = march_init<2>(N, N, a.JT);  // j1 even: N and JT are
+    if (m.j0 >= N) return;
 
     auto load_line = [&](int jj, double (&t)[2]) {
-        const bool ok = act && jj >= 0 && jj < N;  // lines outside the grid are zeros
-        ld_vec<2>(ok ? a.x + (i64)jj * N + i0 : nullptr, ok, t);
+        const bool ok = m.act && jj >= 0 && jj < N;  // lines outside the grid are zeros
+        ld_vec<2>(ok ? a.x + (i64)jj * N + m.i0 : nullptr, ok, t);
     };
 
     if constexpr (!RESID) {
-        for (int j = j0; j < j1; j += 2) {
+        for (int j = m.j0; j < m.j1; j += 2) {
             double f0[2], f1[2];
             load_line(j, f0);
             load_line(j + 1, f1);
             const double s = ((f0[0] + f0[1]) + f1[0]) + f1[1];
-            if (act) a.rc[(i64)(j >> 1) * Nc + (i0 >> 1)] = s;
+            if (m.act) a.rc[(i64)(j >> 1) * Nc + (m.i0 >> 1)] = s;
         }
     } else {
         double tm[2], tc[2], tp[2], tn[2] = {0.0, 0.0};
-        load_line(j0 - 1, tm);
-        load_line(j0, tc);
-        load_line(j0 + 1, tp);
+        load_line(m.j0 - 1, tm);
+        load_line(m.j0, tc);
+        load_line(m.j0 + 1, tp);
         double pend = 0.0;
-        for (int j = j0; j < j1; ++j) {
-            if (j + 2 <= j1) load_line(j + 2, tn);  // in flight while line j is computed
+        for (int j = m.j0; j < m.j1; ++j) {
+            if (j + 2 <= m.j1) load_line(j + 2, tn);  // in flight while line j is computed
             const i64 row = (i64)j * N;
-            double left = __shfl_up(tc[1], 1, 64);    // previous lane's last point
-            double right = __shfl_down(tc[0], 1, 64);  // next lane's first point
-            if (lane == 0 && act) left = (i0 > 0) ? a.x[row + i0 - 1] : 0.0;
-            if (lane == 63 && act) right = (i0 + 2 < N) ? a.x[row + i0 + 2] : 0.0;
-            if (i0 == 0) left = 0.0;
-            if (i0 + 2 >= N) right = 0.0;
+            double left, right;
+            we_load<2, false>(m, N, tc, a.x, row, 1.0, left, right);
             double rv[2], f[2];
-            ld_vec<2>(act ? a.r + row + i0 : nullptr, act, rv);
+            ld_vec<2>(m.act ? a.r + row + m.i0 : nullptr, m.act, rv);
 #pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const double W = (k == 0) ? left : tc[0];
-                const double E = (k == 1) ? right : tc[1];
-                const double s = ((W + E) + tp[k]) + tm[k];
-                const double ax = 4.0 * tc[k] - 1.0 * s;
-                f[k] = rv[k] - ax;
-            }
+            for (int k = 0; k < 2; ++k) f[k] = rv[k] - ax5_at<2>(k, tc, tp, tm, left, right);
             if ((j & 1) == 0) {
                 pend = f[0] + f[1];
             } else {
                 pend = (pend + f[0]) + f[1];
-                if (act) a.rc[(i64)(j >> 1) * Nc + (i0 >> 1)] = pend;
+                if (m.act) a.rc[(i64)(j >> 1) * Nc + (m.i0 >> 1)] = pend;
             }
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
@@ -123,7 +109,8 @@ __global__ __launch_bounds__(TPB) void k_mg_restrict(MgrArgs a) {
 hipError_t mg_restrict(bool fused, int N, const double *x, const double *r, double *rc, hipStream_t st) {
     if (N < 2 || (N & 1) || x == nullptr || rc == nullptr || (fused && r == nullptr)) return hipErrorInvalidValue;
     const int gx = (N + TPB * 2 - 1) / (TPB * 2);
-    // ~2048 workgroups, each marching an even number of lines (k_stencil's sizing)
+    // ~2048 workgroups of at most 64 lines, as set_geometry sizes the stencil sweeps, but an even
+    // number of lines each and no cap on the workgroup count (no partial slab)
     int JT = (int)(((i64)N * gx + 2047) / 2048);
     JT = (JT + 1) & ~1;
     JT = JT < 2 ? 2 : (JT > 64 ? 64 : JT);

@@ -4,7 +4,7 @@
 // sweeps on a smaller square grid, and these three streaming launches move between levels
 // and close the cycle --
 //   mg_restrict     rc(I,J) = ((f(2I,2J) + f(2I+1,2J)) + f(2I,2J+1)) + f(2I+1,2J+1), f stored,
-//                   or f = r - A z formed on the fly in k_stencil's line march (never stored)
+//                   or f = r - A z formed on the fly in gk_march.hpp's line march (never stored)
 //   mg_prolong_add  out(i,j) = z(i,j) + ec(i/2, j/2)
 //   mg_add          out = a + b with the fused dot / norm partials of the launch that writes out
 // -- with no atomics, no grid barrier and no spin wait.  N is the FINE grid's side (even).

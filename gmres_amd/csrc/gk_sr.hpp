@@ -6,8 +6,7 @@
 // the scalars (alpha, beta, omega, the residual) in `single` blocks.  Here one
 // iteration is two (PCG) or three (BiCGSTAB) passes over HBM:
 //
-//   * k_sr_march: a Poisson-5 line march (k_stencil's register scheme: lines
-//     j-1, j, j+1 in registers, W/E neighbours by __shfl) whose OPERAND is
+//   * k_sr_march: a Poisson-5 line march (gk_march.hpp) whose OPERAND is
 //     formed on load from up to three vectors -- p = z + beta p, p = r +
 //     beta (p - omega ap), s = r - alpha ap -- so the vector update that
 //     precedes a stencil in the reference costs no pass of its own, and whose
@@ -31,7 +30,7 @@
 // Element-wise expressions keep the reference's association order (compiled
 // with -ffp-contract=off); only the dot-product summation order differs.
 #pragma once
-#include "gk_common.hpp"  // ld_vec, st_vec
+#include "gk_march.hpp"
 
 namespace gk {
 
@@ -240,23 +239,9 @@ constexpr int sr_nacc() {
 #ifndef GK_SR_NT
 #define GK_SR_NT 62
 #endif
-typedef double sr_d2v __attribute__((ext_vector_type(2)));
-template <bool NT>
-__device__ __forceinline__ double2 sr_ld2(const double *p) {
-    if constexpr (NT) {
-        const sr_d2v t = __builtin_nontemporal_load(reinterpret_cast<const sr_d2v *>(p));
-        return double2{t.x, t.y};
-    } else {
-        return *reinterpret_cast<const double2 *>(p);
-    }
-}
-template <bool NT>
-__device__ __forceinline__ double sr_ld1(const double *p) {
-    if constexpr (NT) return __builtin_nontemporal_load(p);
-    else return *p;
-}
+// The loads: ld_pol (gk_march.hpp), ldv (gk_common.hpp); the stores:
 __device__ __forceinline__ void sr_st2(double *p, double2 v) {
-    if constexpr (GK_SR_NT & 2) __builtin_nontemporal_store(sr_d2v{v.x, v.y}, reinterpret_cast<sr_d2v *>(p));
+    if constexpr (GK_SR_NT & 2) __builtin_nontemporal_store(d2v{v.x, v.y}, reinterpret_cast<d2v *>(p));
     else *reinterpret_cast<double2 *>(p) = v;
 }
 template <int VEC>
@@ -280,11 +265,7 @@ __global__ __launch_bounds__(TPB) void k_sr_march(SrArgs a) {
     const double al = a.sd->alpha, be = a.sd->beta, om = a.sd->omega;
     const double dv = a.cd, ca = a.ca;
     const int N = a.N;
-    const int lane = threadIdx.x & 63;
-    const i64 i0 = (i64)blockIdx.x * (TPB * VEC) + (i64)VEC * threadIdx.x;
-    const bool act = i0 < N;
-    const int j0 = blockIdx.y * a.JT;
-    const int j1 = min(j0 + a.JT, a.nlines);
+    const March m = march_init<VEC>(N, a.nlines, a.JT);
     double acc0 = 0.0, acc1 = 0.0;
 
     auto in_ptr = [&](int v) -> const double * { return v == 0 ? a.in0 : v == 1 ? a.in1 : a.in2; };
@@ -294,25 +275,6 @@ __global__ __launch_bounds__(TPB) void k_sr_march(SrArgs a) {
     // out-of-range values replaced by selects afterwards), so the compiler can wait
     // for exactly the loads a step consumes instead of draining the pipeline at a
     // branch merge.
-    const i64 il = act ? i0 : 0;  // the load column (a lane past N loads column 0, then writes nothing)
-    auto ldr = [&](const double *p, double (&v)[VEC]) {
-        if constexpr (VEC == 2) {
-            const double2 t = sr_ld2<(GK_SR_NT & 1) != 0>(p);
-            v[0] = t.x;
-            v[1] = t.y;
-        } else {
-            v[0] = sr_ld1<(GK_SR_NT & 1) != 0>(p);
-        }
-    };
-    auto lde = [&](const double *p, double (&v)[VEC]) {
-        if constexpr (VEC == 2) {
-            const double2 t = sr_ld2<(GK_SR_NT & 8) != 0>(p);
-            v[0] = t.x;
-            v[1] = t.y;
-        } else {
-            v[0] = sr_ld1<(GK_SR_NT & 8) != 0>(p);
-        }
-    };
     // line jj of input q: own line, halo line, or the zero line past a physical
     // boundary (the operand of zero inputs is +0 in every formula: no select).
     // The halo choice is made once, outside the march.
@@ -325,28 +287,17 @@ __global__ __launch_bounds__(TPB) void k_sr_march(SrArgs a) {
     auto src = [&](int q, int jj) -> const double * {
         return jj < 0 ? lo_[q] : (jj < a.nlines ? in_ptr(q) + (i64)jj * N : (jj == a.nlines ? hi_[q] : a.zl));
     };
-    // operand inputs read here for the last time in the iteration (p, ap of the previous
-    // iteration: CG_P in1, BI_P in1 / in2) may load non-temporally (GK_SR_NT bit 4)
-    auto ldlast = [&](const double *p, double (&v)[VEC]) {
-        if constexpr (VEC == 2) {
-            const double2 t = sr_ld2<(GK_SR_NT & 16) != 0>(p);
-            v[0] = t.x;
-            v[1] = t.y;
-        } else {
-            v[0] = sr_ld1<(GK_SR_NT & 16) != 0>(p);
-        }
-    };
     auto raw_line = [&](int jj, double (&v)[3][VEC]) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            // last use in the iteration: the previous p / ap (CG_P, BI_P in1 / in2); with bit 5
-            // also r in BiCGSTAB's s pass (BI_S in0: bi_x then overwrites it)
+            // last use in the iteration (GK_SR_NT bit 4): the previous p / ap (CG_P, BI_P in1 /
+            // in2); with bit 5 also r in BiCGSTAB's s pass (BI_S in0: bi_x then overwrites it)
             const bool last = (q > 0 && (K == SRK_CG_P || K == SRK_BI_P)) ||
                                   ((GK_SR_NT & 32) != 0 && q == 0 && K == SRK_BI_S);
             if (q < NIN && last) {
-                ldlast(src(q, jj) + il, v[q]);
+                ld_pol<VEC, (GK_SR_NT & 16) != 0>(src(q, jj) + m.il(), v[q]);
             } else if (q < NIN) {
-                ldr(src(q, jj) + il, v[q]);
+                ld_pol<VEC, (GK_SR_NT & 1) != 0>(src(q, jj) + m.il(), v[q]);
             } else {
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) v[q][k] = 0.0;
@@ -357,7 +308,7 @@ __global__ __launch_bounds__(TPB) void k_sr_march(SrArgs a) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
             const double x = sr_operand<K>(v[0][k], v[1][k], v[2][k], al, be, om);
-            u[k] = act ? x : 0.0;
+            u[k] = m.act ? x : 0.0;
             t[k] = CB ? u[k] / dv : u[k];
         }
     };
@@ -370,8 +321,8 @@ __global__ __launch_bounds__(TPB) void k_sr_march(SrArgs a) {
     // 63's (32..62), so the wave's edge load touches two cache lines and never
     // re-reads the lanes' own points through L2 (A/B r06ap: +3-5 % over every lane
     // reloading its own point)
-    const i64 wb0 = i0 - (i64)VEC * lane;  // the wave's first point
-    i64 ei = lane < 32 ? wb0 - 1 : wb0 + 64 * VEC;
+    const i64 wb0 = m.i0 - (i64)VEC * m.lane;  // the wave's first point
+    i64 ei = m.lane < 32 ? wb0 - 1 : wb0 + 64 * VEC;
     ei = ei < 0 ? 0 : (ei >= N ? N - 1 : ei);
     auto edge_ld = [&](int jj, double (&e)[3]) {
         const i64 off = (i64)jj * N + ei;
@@ -379,54 +330,48 @@ __global__ __launch_bounds__(TPB) void k_sr_march(SrArgs a) {
         for (int q = 0; q < 3; ++q) e[q] = q < NIN ? in_ptr(q)[off] : 0.0;
     };
     auto epi_ld = [&](int jj, double (&xv)[VEC], double (&rv)[VEC], double (&vd)[VEC]) {
-        const i64 off = (i64)jj * N + il;
+        const i64 off = (i64)jj * N + m.il();
+        constexpr bool NT = (GK_SR_NT & 8) != 0;
         if (K == SRK_CG_X) {
-            lde(a.x + off, xv);
-            lde(a.r + off, rv);
+            ld_pol<VEC, NT>(a.x + off, xv);
+            ld_pol<VEC, NT>(a.r + off, rv);
         }
-        if (VD) lde(a.vd + off, vd);
+        if (VD) ld_pol<VEC, NT>(a.vd + off, vd);
     };
 
-    if (j0 < a.nlines) {
+    if (m.j0 < a.nlines) {
         double uc[VEC], up[VEC], tm[VEC], tc[VEC], tp[VEC], scratch[VEC];
         {
             double v[3][VEC];
-            raw_line(j0 - 1, v);
+            raw_line(m.j0 - 1, v);
             form(v, scratch, tm);
-            raw_line(j0, v);
+            raw_line(m.j0, v);
             form(v, uc, tc);
-            raw_line(j0 + 1, v);
+            raw_line(m.j0 + 1, v);
             form(v, up, tp);
         }
         // in flight: operand inputs of line j+2, epilogue operands of line j+1
         double rw[3][VEC];
         double xq[VEC] = {}, rq[VEC] = {}, vq[VEC] = {};
         double xc[VEC] = {}, rc[VEC] = {}, vc[VEC] = {}, ec[3] = {};
-        epi_ld(j0, xc, rc, vc);
-        edge_ld(j0, ec);
-        for (int j = j0; j < j1; ++j) {
+        epi_ld(m.j0, xc, rc, vc);
+        edge_ld(m.j0, ec);
+        for (int j = m.j0; j < m.j1; ++j) {
             // issue: operand inputs of line j+2 (unused past the block's last line),
             // epilogue and edge inputs of line j+1 (line j stands in past the last)
-            const int jn = j + 1 < j1 ? j + 1 : j;
+            const int jn = j + 1 < m.j1 ? j + 1 : j;
             raw_line(j + 2, rw);
             epi_ld(jn, xq, rq, vq);
             double en[3] = {};
             edge_ld(jn, en);
             const i64 row = (i64)j * N;
-            double left = __shfl_up(tc[VEC - 1], 1, 64);
-            double right = __shfl_down(tc[0], 1, 64);
-            const double et = edge_t(ec);
-            left = lane == 0 ? et : left;
-            right = lane == 63 ? et : right;
-            left = i0 == 0 ? 0.0 : left;
-            right = i0 + VEC >= N ? 0.0 : right;
+            double left, right;
+            we_shfl<VEC>(tc, left, right);
+            we_edge<VEC>(m, N, m.lane == 0, m.lane == 63, edge_t(ec), left, right);
             double yv[VEC];
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
-                const double W = (k == 0) ? left : tc[k - 1];
-                const double E = (k == VEC - 1) ? right : tc[k + 1];
-                const double s = ((W + E) + tp[k]) + tm[k];
-                const double ax = 4.0 * tc[k] - 1.0 * s;
+                const double ax = ax5_at<VEC>(k, tc, tp, tm, left, right);
                 if constexpr (CB) {
                     yv[k] = tc[k] + ca * (uc[k] - ax);
                 } else {
@@ -437,26 +382,26 @@ __global__ __launch_bounds__(TPB) void k_sr_march(SrArgs a) {
                     rc[k] = rc[k] - al * ax;
                 }
             }
-            if (act) {
-                if (WU) sr_stv<VEC>(a.ou + row + i0, uc);
-                if (WY) sr_stv<VEC>(a.oy + row + i0, yv);
+            if (m.act) {
+                if (WU) sr_stv<VEC>(a.ou + row + m.i0, uc);
+                if (WY) sr_stv<VEC>(a.oy + row + m.i0, yv);
                 if (K == SRK_CG_X) {
-                    sr_stv<VEC>(a.x + row + i0, xc);
-                    sr_stv<VEC>(a.r + row + i0, rc);
+                    sr_stv<VEC>(a.x + row + m.i0, xc);
+                    sr_stv<VEC>(a.r + row + m.i0, rc);
                 }
             }
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {  // a lane past N contributes exact zeros (u = 0)
                 if constexpr (K == SRK_CG_P) acc0 = acc0 + yv[k] * uc[k];
-                else if constexpr (K == SRK_CG_X) acc0 = act ? acc0 + rc[k] * rc[k] : acc0;
-                else if constexpr (K == SRK_CG_Z) acc0 = act ? acc0 + uc[k] * yv[k] : acc0;
-                else if constexpr (K == SRK_BI_P || K == SRK_ST1) acc0 = act ? acc0 + yv[k] * vc[k] : acc0;
+                else if constexpr (K == SRK_CG_X) acc0 = m.act ? acc0 + rc[k] * rc[k] : acc0;
+                else if constexpr (K == SRK_CG_Z) acc0 = m.act ? acc0 + uc[k] * yv[k] : acc0;
+                else if constexpr (K == SRK_BI_P || K == SRK_ST1) acc0 = m.act ? acc0 + yv[k] * vc[k] : acc0;
                 else if constexpr (K == SRK_BI_S) {
-                    acc0 = act ? acc0 + yv[k] * uc[k] : acc0;
-                    acc1 = act ? acc1 + yv[k] * yv[k] : acc1;
+                    acc0 = m.act ? acc0 + yv[k] * uc[k] : acc0;
+                    acc1 = m.act ? acc1 + yv[k] * yv[k] : acc1;
                 } else if constexpr (K == SRK_ST2) {
-                    acc0 = act ? acc0 + yv[k] * vc[k] : acc0;
-                    acc1 = act ? acc1 + yv[k] * yv[k] : acc1;
+                    acc0 = m.act ? acc0 + yv[k] * vc[k] : acc0;
+                    acc1 = m.act ? acc1 + yv[k] * yv[k] : acc1;
                 }
             }
             // line j+2's operand, formed now that line j is done; the rings advance
@@ -484,9 +429,8 @@ __global__ __launch_bounds__(TPB) void k_sr_march(SrArgs a) {
 // Two-level marches (single rank, gk_sr_* with cbpr2): the preconditioner and
 // the operator next to it in ONE pass.  Level 1 is computed one line ahead of
 // level 2 (line j+1 at step j), so level 2 finds its three lines in registers;
-// the W/E neighbours across windows come from the edge lanes, which compute the
-// level-1 value of the point beyond their window themselves (two edge columns:
-// ea next to the window, eb one further).  Every element-wise expression, the
+// the edge lanes compute the level-1 value of the point beyond their window
+// themselves (edge2_init, grouped loads).  Every element-wise expression, the
 // stencil's association order and the per-workgroup dot order are those of the
 // one-level passes it replaces, on the same grid: the results are bit-identical
 // to SRK_CG_X + SRK_CG_Z, SRK_BI_PC + SRK_ST1, SRK_BI_SC + SRK_ST2.  Halo lines
@@ -506,12 +450,6 @@ constexpr int sr2_nin() {
     return K2 == SR2_BI_P ? 3 : K2 == SR2_BI_S ? 2 : 1;
 }
 
-// A t at one point, k_stencil's order: 4 tc - (((W + E) + N) + S)   (poisson.f90:42)
-__device__ __forceinline__ double sr_ax(double tc, double W, double E, double tN, double tS) {
-    const double s = ((W + E) + tN) + tS;
-    return 4.0 * tc - 1.0 * s;
-}
-
 template <int VEC, int K2>
 __global__ __launch_bounds__(TPB) void k_sr_march2(SrArgs a) {
     __shared__ double sm[WAVES];
@@ -523,68 +461,31 @@ __global__ __launch_bounds__(TPB) void k_sr_march2(SrArgs a) {
     const double al = a.sd->alpha, be = a.sd->beta, om = a.sd->omega;
     const double dv = a.cd, ca = a.ca;
     const int N = a.N, nl = a.nlines;
-    const int lane = threadIdx.x & 63;
-    const i64 i0 = (i64)blockIdx.x * (TPB * VEC) + (i64)VEC * threadIdx.x;
-    const bool act = i0 < N;
-    const int j0 = blockIdx.y * a.JT;
-    const int j1 = min(j0 + a.JT, nl);
-    const i64 il = act ? i0 : 0;
-    // edge columns: ea next to the window (lane 0: left, lane 63: right), eb one further
-    const bool e0l = lane == 0, e63 = lane == 63;
-    const i64 wb0 = i0 - (i64)VEC * lane;  // the wave's first point (edge loads grouped as in k_sr_march)
-    i64 ea = lane < 32 ? wb0 - 1 : wb0 + 64 * VEC;
-    i64 eb = lane < 32 ? wb0 - 2 : wb0 + 64 * VEC + 1;
-    const bool eb_ok = e0l ? (i0 - 2 >= 0) : (e63 ? (i0 + VEC + 1 < N) : true);
-    ea = ea < 0 ? 0 : (ea >= N ? N - 1 : ea);
-    eb = eb < 0 ? 0 : (eb >= N ? N - 1 : eb);
+    const March m = march_init<VEC>(N, nl, a.JT);
+    const Edge2 e = edge2_init<VEC, true>(m, N);
+    constexpr bool NTE = (GK_SR_NT & 8) != 0;  // epilogue operands
     const double *in[3] = {a.in0, a.in1, a.in2};
     auto src = [&](const double *b, int jj) -> const double * {
         return (jj >= 0 && jj < nl) ? b + (i64)jj * N : a.zl;
-    };
-    auto ld = [&](const double *p, double (&v)[VEC]) {
-        if constexpr (VEC == 2) {
-            const double2 t = sr_ld2<(GK_SR_NT & 1) != 0>(p);
-            v[0] = t.x;
-            v[1] = t.y;
-        } else {
-            v[0] = sr_ld1<(GK_SR_NT & 1) != 0>(p);
-        }
-    };
-    auto lde = [&](const double *p, double (&v)[VEC]) {
-        if constexpr (VEC == 2) {
-            const double2 t = sr_ld2<(GK_SR_NT & 8) != 0>(p);
-            v[0] = t.x;
-            v[1] = t.y;
-        } else {
-            v[0] = sr_ld1<(GK_SR_NT & 8) != 0>(p);
-        }
     };
     // raw operand inputs of one line: own points, ea, eb
     struct Raw {
         double v[3][VEC], a[3], b[3];
     };
-    auto ldl = [&](const double *p, double (&v)[VEC]) {  // last-use inputs (GK_SR_NT bit 5)
-        if constexpr (VEC == 2) {
-            const double2 t = sr_ld2<(GK_SR_NT & 32) != 0>(p);
-            v[0] = t.x;
-            v[1] = t.y;
-        } else {
-            v[0] = sr_ld1<(GK_SR_NT & 32) != 0>(p);
-        }
-    };
     auto raw = [&](int jj, Raw &w) {
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            // last use in the iteration: the previous p / ap (BI_P in1 / in2), r in the s pass (BI_S in0)
+            // last use in the iteration (GK_SR_NT bit 5): the previous p / ap (BI_P in1 / in2), r in
+            // the s pass (BI_S in0)
             const bool last = (K2 == SR2_BI_P && q > 0) || (K2 == SR2_BI_S && q == 0);
             if (q < NIN) {
                 const double *l = src(in[q], jj);
                 if (last)
-                    ldl(l + il, w.v[q]);
+                    ld_pol<VEC, (GK_SR_NT & 32) != 0>(l + m.il(), w.v[q]);
                 else
-                    ld(l + il, w.v[q]);
-                w.a[q] = l[ea];
-                w.b[q] = l[eb];
+                    ld_pol<VEC, (GK_SR_NT & 1) != 0>(l + m.il(), w.v[q]);
+                w.a[q] = l[e.ea];
+                w.b[q] = l[e.eb];
             } else {
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) w.v[q][k] = 0.0;
@@ -600,13 +501,13 @@ __global__ __launch_bounds__(TPB) void k_sr_march2(SrArgs a) {
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
             const double x = sr_operand<OPK>(w.v[0][k], w.v[1][k], w.v[2][k], al, be, om);
-            o.u[k] = act ? x : 0.0;
+            o.u[k] = m.act ? x : 0.0;
             o.t[k] = CG ? o.u[k] : o.u[k] / dv;
         }
         o.ua = sr_operand<OPK>(w.a[0], w.a[1], w.a[2], al, be, om);
         o.ta = CG ? o.ua : o.ua / dv;
         const double ub = sr_operand<OPK>(w.b[0], w.b[1], w.b[2], al, be, om);
-        o.tb = eb_ok ? (CG ? ub : ub / dv) : 0.0;
+        o.tb = e.eb_ok ? (CG ? ub : ub / dv) : 0.0;
     };
     // level-1 line: v1 and its stencil argument t2 (= v1 / d for cbpr2 at level 2)
     struct Vl {
@@ -619,8 +520,8 @@ __global__ __launch_bounds__(TPB) void k_sr_march2(SrArgs a) {
     auto rld = [&](int jj, Rl &o) {
         if constexpr (CG) {
             const double *l = src(a.r, jj);
-            lde(l + il, o.v);
-            o.a = l[ea];
+            ld_pol<VEC, NTE>(l + m.il(), o.v);
+            o.a = l[e.ea];
         } else {
 #pragma unroll
             for (int k = 0; k < VEC; ++k) o.v[k] = 0.0;
@@ -629,105 +530,93 @@ __global__ __launch_bounds__(TPB) void k_sr_march2(SrArgs a) {
     };
     // level 1 at line jj (centre c, neighbours s = jj-1, n = jj+1)
     auto lev1 = [&](int jj, const Ul &us, const Ul &uc, const Ul &un, const Rl &rr, Vl &o) {
-        double left = __shfl_up(uc.t[VEC - 1], 1, 64);
-        double right = __shfl_down(uc.t[0], 1, 64);
-        left = e0l ? uc.ta : left;
-        right = e63 ? uc.ta : right;
-        left = i0 == 0 ? 0.0 : left;
-        right = i0 + VEC >= N ? 0.0 : right;
+        double left, right;
+        we_select<VEC>(m, e, N, uc.t, uc.ta, left, right);
         const bool lv = jj >= 0 && jj < nl;
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
-            const double W = (k == 0) ? left : uc.t[k - 1];
-            const double E = (k == VEC - 1) ? right : uc.t[k + 1];
-            const double ax = sr_ax(uc.t[k], W, E, un.t[k], us.t[k]);
+            const double ax = ax5_at<VEC>(k, uc.t, un.t, us.t, left, right);
             const double v = CG ? rr.v[k] - al * ax : uc.t[k] + ca * (uc.u[k] - ax);
-            o.v[k] = (lv && act) ? v : 0.0;
+            o.v[k] = (lv && m.act) ? v : 0.0;
             o.t[k] = CG ? o.v[k] / dv : o.v[k];
         }
         // the edge point ea: lane 0 -> W = eb, E = own point 0; lane 63 -> W = own point VEC-1, E = eb
-        const double Wa = e0l ? uc.tb : uc.t[VEC - 1];
-        const double Ea = e0l ? uc.t[0] : uc.tb;
-        const double axa = sr_ax(uc.ta, Wa, Ea, un.ta, us.ta);
+        const double Wa = e.e0 ? uc.tb : uc.t[VEC - 1];
+        const double Ea = e.e0 ? uc.t[0] : uc.tb;
+        const double axa = ax5(uc.ta, Wa, Ea, un.ta, us.ta);
         const double va = CG ? rr.a - al * axa : uc.ta + ca * (uc.ua - axa);
         o.va = lv ? va : 0.0;
         o.ta = CG ? o.va / dv : o.va;
     };
     double acc0 = 0.0, acc1 = 0.0;
-    if (j0 < nl) {
+    if (m.j0 < nl) {
         Ul u0, u1, u2;  // lines j, j+1, j+2
         Vl vm, vc;      // level 1 at lines j-1, j
         Rl rc;          // CG: r of line j+1
         {
             Raw w0, w1, w2, w3, w4;
             Rl ra, rb;
-            raw(j0 - 2, w0);
-            raw(j0 - 1, w1);
-            raw(j0, w2);
-            raw(j0 + 1, w3);
-            raw(j0 + 2, w4);
-            rld(j0 - 1, ra);
-            rld(j0, rb);
-            rld(j0 + 1, rc);
+            raw(m.j0 - 2, w0);
+            raw(m.j0 - 1, w1);
+            raw(m.j0, w2);
+            raw(m.j0 + 1, w3);
+            raw(m.j0 + 2, w4);
+            rld(m.j0 - 1, ra);
+            rld(m.j0, rb);
+            rld(m.j0 + 1, rc);
             Ul um2, um1;
             form(w0, um2);
             form(w1, um1);
             form(w2, u0);
             form(w3, u1);
             form(w4, u2);
-            lev1(j0 - 1, um2, um1, u0, ra, vm);
-            lev1(j0, um1, u0, u1, rb, vc);
+            lev1(m.j0 - 1, um2, um1, u0, ra, vm);
+            lev1(m.j0, um1, u0, u1, rb, vc);
         }
         double xc[VEC] = {}, dc[VEC] = {};
         auto epi = [&](int jj, double (&xv)[VEC], double (&dd)[VEC]) {
-            const i64 off = (i64)jj * N + il;
-            if constexpr (CG) lde(a.x + off, xv);
-            if constexpr (K2 == SR2_BI_P) lde(a.vd + off, dd);
+            const i64 off = (i64)jj * N + m.il();
+            if constexpr (CG) ld_pol<VEC, NTE>(a.x + off, xv);
+            if constexpr (K2 == SR2_BI_P) ld_pol<VEC, NTE>(a.vd + off, dd);
         };
-        epi(j0, xc, dc);
-        for (int j = j0; j < j1; ++j) {
+        epi(m.j0, xc, dc);
+        for (int j = m.j0; j < m.j1; ++j) {
             // issue: raw inputs of line j+3, r of line j+2, epilogue of line j+1 (line j stands in past the last)
             Raw wn;
             raw(j + 3, wn);
             Rl rn;
             rld(j + 2, rn);
             double xn[VEC] = {}, dn[VEC] = {};
-            epi(j + 1 < j1 ? j + 1 : j, xn, dn);
+            epi(j + 1 < m.j1 ? j + 1 : j, xn, dn);
             Vl vp;  // level 1 at line j+1
             lev1(j + 1, u0, u1, u2, rc, vp);
             // level 2 at line j
-            double left = __shfl_up(vc.t[VEC - 1], 1, 64);
-            double right = __shfl_down(vc.t[0], 1, 64);
-            left = e0l ? vc.ta : left;
-            right = e63 ? vc.ta : right;
-            left = i0 == 0 ? 0.0 : left;
-            right = i0 + VEC >= N ? 0.0 : right;
+            double left, right;
+            we_select<VEC>(m, e, N, vc.t, vc.ta, left, right);
             double y[VEC];
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
-                const double W = (k == 0) ? left : vc.t[k - 1];
-                const double E = (k == VEC - 1) ? right : vc.t[k + 1];
-                const double ax = sr_ax(vc.t[k], W, E, vp.t[k], vm.t[k]);
+                const double ax = ax5_at<VEC>(k, vc.t, vp.t, vm.t, left, right);
                 y[k] = CG ? vc.t[k] + ca * (vc.v[k] - ax) : ax;
                 if constexpr (CG) xc[k] = xc[k] + al * u0.u[k];
             }
             const i64 row = (i64)j * N;
-            if (act) {
-                if constexpr (!CG) sr_stv<VEC>(a.ou + row + i0, u0.u);
-                sr_stv<VEC>(a.oy + row + i0, vc.v);
-                sr_stv<VEC>(a.oz + row + i0, y);
-                if constexpr (CG) sr_stv<VEC>(a.x + row + i0, xc);
+            if (m.act) {
+                if constexpr (!CG) sr_stv<VEC>(a.ou + row + m.i0, u0.u);
+                sr_stv<VEC>(a.oy + row + m.i0, vc.v);
+                sr_stv<VEC>(a.oz + row + m.i0, y);
+                if constexpr (CG) sr_stv<VEC>(a.x + row + m.i0, xc);
             }
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 if constexpr (CG) {  // cg_x's <r, r> then cg_z's <r, z>
-                    acc0 = act ? acc0 + vc.v[k] * vc.v[k] : acc0;
-                    acc1 = act ? acc1 + vc.v[k] * y[k] : acc1;
+                    acc0 = m.act ? acc0 + vc.v[k] * vc.v[k] : acc0;
+                    acc1 = m.act ? acc1 + vc.v[k] * y[k] : acc1;
                 } else if constexpr (K2 == SR2_BI_P) {  // st1: <ap, r0>
-                    acc0 = act ? acc0 + y[k] * dc[k] : acc0;
+                    acc0 = m.act ? acc0 + y[k] * dc[k] : acc0;
                 } else {  // st2: <as, s>, <as, as>
-                    acc0 = act ? acc0 + y[k] * u0.u[k] : acc0;
-                    acc1 = act ? acc1 + y[k] * y[k] : acc1;
+                    acc0 = m.act ? acc0 + y[k] * u0.u[k] : acc0;
+                    acc1 = m.act ? acc1 + y[k] * y[k] : acc1;
                 }
             }
             // advance: line j+3 formed now that line j is done
@@ -760,7 +649,7 @@ __global__ __launch_bounds__(TPB) void k_sr_vec(SrArgs a, i64 n) {
     const i64 n2 = n >> 1;
     const i64 step = (i64)gridDim.x * TPB * U;
     double acc0 = 0.0, acc1 = 0.0;
-    auto L = [](const double *p, i64 e) { return sr_ld2<(GK_SR_NT & 4) != 0>(p + 2 * e); };
+    auto L = [](const double *p, i64 e) { return ldv<(GK_SR_NT & 4) != 0>(reinterpret_cast<const double2 *>(p + 2 * e)); };
     for (i64 b = (i64)blockIdx.x * TPB * U + threadIdx.x; b < n2; b += step) {
         double2 v0[U], v1[U], v2[U], v3[U], v4[U], v5[U];
 #pragma unroll

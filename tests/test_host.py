@@ -3,6 +3,7 @@ library load and export every declared symbol, argument validation fails
 loudly, the slab decomposition is sound."""
 import ctypes
 import os
+import re
 import subprocess
 import sys
 
@@ -97,6 +98,27 @@ def test_product_does_not_import_oracle():
                 txt = open(os.path.join(dirpath, f)).read()
                 for bad in ("import oracle", "from oracle", "liboracle", "gmres_oracle", "or_gmres", "or_stvec"):
                     assert bad not in txt, (f, bad)
+
+
+def test_line_march_is_stated_once():
+    """The 5-point operator's point formula, 4 c - 1 (((W + E) + N) + S), and the __shfl pair that
+    fetches a lane's W/E neighbours are written in gk_march.hpp alone: every marching kernel calls
+    them there.  The Chebyshev pass keeps the same formula as one exact fma in gk_cheb.hip."""
+    csrc = os.path.join(ROOT, "gmres_amd", "csrc")
+    formula = re.compile(r"4\.0\s*\*[^;\n]*-\s*1\.0\s*\*")
+    fma = re.compile(r"fma\(\s*4\.0\s*,")
+    shfl, stated, fused = [], [], []
+    for f in sorted(os.listdir(csrc)):
+        txt = open(os.path.join(csrc, f)).read()
+        if "__shfl_up" in txt:
+            shfl.append(f)
+        if formula.search(txt):
+            stated.append(f)
+        if fma.search(txt):
+            fused.append(f)
+    assert shfl == ["gk_march.hpp"], shfl
+    assert stated == ["gk_march.hpp"], stated
+    assert fused == ["gk_cheb.hip"], fused
 
 
 def test_build_refuses_chebyshev_scratch_spills():
