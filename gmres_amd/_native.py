@@ -117,6 +117,8 @@ _SIGS = {
     "gk_mg_info": (c_int, [c_vp, _ip]),
     "gk_mg_transfer": (c_int, [c_vp, c_int, c_int, _dp, _dp, _dp]),
     "gk_set_precond_side": (c_int, [c_vp, c_int]),
+    "gk_set_shift": (c_int, [c_vp, c_double]),
+    "gk_get_shift": (c_int, [c_vp, _dp]),
     "gk_set_basis_precision": (c_int, [c_vp, c_int]),
     "gk_get_basis_precision": (c_int, [c_vp, _ip]),
     "gk_cb_plan_query": (c_int, [c_ll, c_int, c_int, c_int, ctypes.POINTER(c_ll)]),
@@ -165,6 +167,7 @@ _SIGS = {
     "gk_sr_status": (c_int, [c_vp, c_int, _ip, _ip, _dp]),
     "gk_sr_history": (c_int, [c_vp, _dp, c_int]),
     "gk_poisson5": (c_int, [c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "gk_poisson5_shift": (c_int, [c_int, c_int, c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "gk_precond_apply": (c_int, [c_int, c_int, _dp, c_int, c_vp, c_vp, c_vp, c_vp]),
     "gk_mgs_project": (c_int, [c_ll, c_vp, c_vp, c_vp, c_vp]),
     "gk_dot": (c_int, [c_ll, c_vp, c_vp, c_vp, c_vp]),

@@ -350,6 +350,27 @@ int gk_set_precond_side(gk_ctx *c, int side) {
     return GK_OK;
 }
 
+// A := A_poisson + sigma I.  The open cycle's basis and a running gk_sr_* solve belong to the
+// other operator; captured steps hold diag (and the multigrid levels' coefficients) by value.
+int gk_set_shift(gk_ctx *c, double sigma) {
+    CHK(check_ctx(c));
+    if (!(sigma >= 0.0) || !(sigma <= 1e12))  // NaN fails both
+        return set_err(GK_ERR_ARG, "shift %g outside 0 .. 1e12", sigma);
+    sr_invalidate(c);
+    c->cycle_mgs = c->cycle_hh = false;
+    if (sigma != c->shift) graph_reset(c);
+    c->shift = sigma;
+    mg_refresh(c);
+    return GK_OK;
+}
+
+int gk_get_shift(gk_ctx *c, double *sigma) {
+    CHK(check_ctx(c));
+    if (sigma == nullptr) return set_err(GK_ERR_ARG, "null sigma");
+    *sigma = c->shift;
+    return GK_OK;
+}
+
 int gk_set_basis_precision(gk_ctx *c, int prec) {
     CHK(check_ctx(c));
     if (prec != GK_BASIS_F64 && prec != GK_BASIS_F32) return set_err(GK_ERR_ARG, "bad basis precision %d", prec);
@@ -791,7 +812,7 @@ int gk_mg_plan_query(int nside, int *info) {
     const int nl = gk::mg_levels(nside, sides);
     if (nl < 2) return set_err(GK_ERR_ARG, "multigrid needs an even N with N / 2 >= %d (N = %d)", gk::MG_NMIN, nside);
     double lo, hi;
-    mg_info_fill(sides, nl, gk::mg_coarse_degree(sides[nl - 1], &lo, &hi), 0, info);
+    mg_info_fill(sides, nl, gk::mg_coarse_degree(sides[nl - 1], 0.0, &lo, &hi), 0, info);
     return GK_OK;
 }
 
@@ -893,16 +914,23 @@ bool aligned16(const void *p) { return p == nullptr || (reinterpret_cast<uintptr
 
 extern "C" {
 
-int gk_poisson5(int nside, int nlines, const double *x, const double *hlo, const double *hhi, double *y,
-                void *stream) {
+int gk_poisson5_shift(int nside, int nlines, double sigma, const double *x, const double *hlo, const double *hhi,
+                      double *y, void *stream) {
     if (nside < 2 || nlines < 1 || x == nullptr || y == nullptr) return set_err(GK_ERR_ARG, "bad poisson5 args");
+    if (!(sigma >= 0.0) || !(sigma <= 1e12)) return set_err(GK_ERR_ARG, "shift %g outside 0 .. 1e12", sigma);
     if (!aligned16(x) || !aligned16(y) || !aligned16(hlo) || !aligned16(hhi))
         return set_err(GK_ERR_ARG, "device pointers must be 16-byte aligned");
     gk_ctx c;
     CHK(stateless_ctx(c, nside, nlines, (i64)nside * nlines, stream));
+    c.shift = sigma;
     const int rc = stencil_plain_raw(&c, x, hlo, hhi, y);
     release_stateless(c);
     return rc;
+}
+
+int gk_poisson5(int nside, int nlines, const double *x, const double *hlo, const double *hhi, double *y,
+                void *stream) {
+    return gk_poisson5_shift(nside, nlines, 0.0, x, hlo, hhi, y, stream);
 }
 
 int gk_precond_apply(int nside, int kind, const double *params, int degree, const double *r, double *z,

@@ -11,12 +11,13 @@
 
 namespace gk {
 
-// 4c - s as ONE fma: 4c is exact (a power-of-two scale), so fma(4, c, -s)
-// rounds the same real number once, exactly as (4c) - s does -- bit-identical
-// to the per-sweep kernel and the oracle, one FP64 instruction per point and
-// level fewer in the issue-bound level chain (116.4 -> 110.7 us per pass against the
-// multiply + subtract, profiles/r06/ab_cf_fma4_r06bc.txt).
-__device__ __forceinline__ double cf_4c_minus(double c, double s) { return __builtin_fma(4.0, c, -s); }
+// diag c - s as ONE fma, diag = fl(4 + shift) from CFArgs (uniform: scalar registers), the
+// expression of gk_march.hpp's ax5 -- bit-identical to the per-sweep kernel for every shift.
+// At diag = 4 it is fma(4.0, c, -s): the product is exact (a power-of-two scale), so the one
+// rounding is that of (4c) - s and of the oracle; one FP64 instruction per point and level fewer in the
+// issue-bound level chain than multiply + subtract (116.4 -> 110.7 us per pass,
+// profiles/r06/ab_cf_fma4_r06bc.txt).
+__device__ __forceinline__ double cf_dc_minus(double diag, double c, double s) { return __builtin_fma(diag, c, -s); }
 
 
 // Lane i gets lane i-1's value (lane 0 gets 0) / lane i+1's (lane 63 gets 0).
@@ -198,7 +199,7 @@ __global__ __launch_bounds__(CF_W) __attribute__((amdgpu_waves_per_eu(CF_OCC, CF
                 const double W0 = cf_from_left(C1), E1 = cf_from_right(C0);
                 const double s0 = ((W0 + C1) + vw[SN][0]) + vw[SS][0];
                 const double s1 = ((C0 + E1) + vw[SN][1]) + vw[SS][1];
-                const double ax0 = cf_4c_minus(C0, s0), ax1 = cf_4c_minus(C1, s1);
+                const double ax0 = cf_dc_minus(a.diag, C0, s0), ax1 = cf_dc_minus(a.diag, C1, s1);
                 nd0 = ax0 / a.theta;
                 nd1 = ax1 / a.theta;
                 nr0 = ax0;
@@ -247,7 +248,7 @@ __global__ __launch_bounds__(CF_W) __attribute__((amdgpu_waves_per_eu(CF_OCC, CF
                 const double W0 = cf_from_left(C1), E1 = cf_from_right(C0);
                 const double s0 = ((W0 + C1) + d[l][SN][0]) + d[l][SS][0];
                 const double s1 = ((C0 + E1) + d[l][SN][1]) + d[l][SS][1];
-                const double ad0 = cf_4c_minus(C0, s0), ad1 = cf_4c_minus(C1, s1);
+                const double ad0 = cf_dc_minus(a.diag, C0, s0), ad1 = cf_dc_minus(a.diag, C1, s1);
                 const double res0 = r[l][QC][0] - ad0, res1 = r[l][QC][1] - ad1;
                 double dn0 = a.c1[l] * C0 + a.c2[l] * res0, dn1 = a.c1[l] * C1 + a.c2[l] * res1;
                 // z of level 0 in the first pass equals its d (z0 = d0)

@@ -49,6 +49,7 @@ struct CFArgs {
     const double *vdot;  // ACC_DOT partner
     double *part;
     double theta;        // FIRST: d0 = r / theta
+    double diag;         // the operator's diagonal, fl(4 + shift)
     double c1[CF_LMAX], c2[CF_LMAX];
     int N, nlines, JT;
     // Row-block slabs (deep halo): L grid lines of each input from the slab

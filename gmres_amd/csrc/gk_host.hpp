@@ -75,6 +75,7 @@ struct gk_ctx {
     // preconditioner
     int pkind = GK_PREC_IDENTITY, pdeg = 8;
     double p0 = 8.2, p1 = 0.2;
+    double shift = 0.0;        // the operator is A_poisson + shift I (gk_set_shift; a multigrid level's: 4^l times it)
     int side = GK_SIDE_LEFT;   // MGS-R: left (the reference) or right preconditioning (gk_set_precond_side)
     int tune_right_fused = 1;  // side right, cbpr2, one rank: w = A M^-1 v as one march (k_right_cbpr2)
     int basis = GK_BASIS_F64;  // MGS-R: storage precision of the Krylov columns (gk_set_basis_precision, gk_cb.hpp)
@@ -85,6 +86,8 @@ struct gk_ctx {
     std::vector<gk_mg_level> mg;                   // GK_PREC_MG: levels 0 .. L (empty otherwise)
     double *mg_buf = nullptr;                      // ... their vectors, one allocation
     int mg_cdeg = 0;                               // ... the coarsest level's sweep count
+    double mg_p0 = 0.0, mg_p1 = 0.0;               // ... level 0's smoother interval as gk_set_precond gave it
+    int mg_deg = 0;                                // ... and the smoother degree (mg_refresh)
     int tune_mg_fused = 1;                         // GK_TUNE_MG_FUSED: residual and restriction in one march
     // decomposition / comm
     int nranks = 1, rank = 0, max_lines = 0;
@@ -230,6 +233,9 @@ inline int check_nout(const gk_ctx *c, int n_out) {
 // running gk_sr_* solve -- later gk_sr_iterate / status / history refuse until the
 // next gk_sr_start.
 inline void sr_invalidate(gk_ctx *c) { c->sr_solver = -1; }
+// The diagonal of the context's operator A_poisson + shift I, the `diag` every stencil-carrying
+// kernel takes: fl(4 + shift), rounded once here and never in a kernel.
+inline double diag_of(const gk_ctx *c) { return 4.0 + c->shift; }
 // The context's side: the MGS-R cycle's.  The short-recurrence solvers and Householder's
 // GK_HH_PREC_LEFT precondition on the left only; GK_HH_PREC_RIGHT does not ask the context.
 inline bool right_prec(const gk_ctx *c) { return c->side == GK_SIDE_RIGHT && c->pkind != GK_PREC_IDENTITY; }
@@ -268,6 +274,7 @@ int add_precond_sweeps(gk_ctx *c, const double *t);  // ... always the sweeps in
 // GK_PREC_MG: the hierarchy of a whole-grid single-rank context (built by gk_set_precond, freed
 // by it and by gk_destroy), the V-cycle behind precond_sweeps, and gk_mg_transfer's launches
 int mg_build(gk_ctx *c, double p0, double p1, int degree);
+void mg_refresh(gk_ctx *c);  // the levels' shift, intervals and coarsest degree from c->shift (no allocation)
 void mg_free(gk_ctx *c);
 int mg_apply(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part);
 int mg_transfer(gk_ctx *c, int what, int level, const double *a, const double *b, double *out);

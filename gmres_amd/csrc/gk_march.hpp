@@ -24,27 +24,29 @@
 //   * Line tiles: a tile re-reads lines j0-1 and j1 (two-level: j0-2 .. j1+1).
 //   * Lanes past the line's end (act false) load nothing or column 0 (il) and store nothing.
 //
-// The Chebyshev pass (gk_cheb.hip: cf_4c_minus and its DPP neighbours) states the same
-// point formula as one exact fma: whoever changes the operator changes it there too.
+// The Chebyshev pass (gk_cheb.hip: cf_dc_minus and its DPP neighbours) states the same
+// point formula, the same one fma: whoever changes the operator changes it there too.
 #pragma once
 #include "gk_common.hpp"
 
 namespace gk {
 
-// A t at one point: 4 c - (((W + E) + N) + S)   (poisson.f90:42)
-__device__ __forceinline__ double ax5(double c, double W, double E, double n, double s) {
+// A t at one point: diag c - (((W + E) + N) + S) as ONE fused multiply-add, diag = fl(4 + shift)
+// a kernel argument (gk_host.hpp: diag_of).  At diag = 4 the product is exact, so the one
+// rounding gives the double of the reference's two, 4.0 * c - 1.0 * sum   (poisson.f90:42)
+__device__ __forceinline__ double ax5(double diag, double c, double W, double E, double n, double s) {
     const double sum = ((W + E) + n) + s;
-    return 4.0 * c - 1.0 * sum;
+    return __builtin_fma(diag, c, -sum);
 }
 
 // ... at point k of a lane's line tc (tp: line j+1, tm: line j-1); left / right: the W / E
 // neighbours of the lane's first / last point
 template <int VEC>
-__device__ __forceinline__ double ax5_at(int k, const double (&tc)[VEC], const double (&tp)[VEC],
+__device__ __forceinline__ double ax5_at(double diag, int k, const double (&tc)[VEC], const double (&tp)[VEC],
                                          const double (&tm)[VEC], double left, double right) {
     const double W = (k == 0) ? left : tc[k - 1];
     const double E = (k == VEC - 1) ? right : tc[k + 1];
-    return ax5(tc[k], W, E, tp[k], tm[k]);
+    return ax5(diag, tc[k], W, E, tp[k], tm[k]);
 }
 
 // A lane's window: its first point i0 (act: inside the line) and the workgroup's lines

@@ -27,14 +27,15 @@ int mg_levels(int N, int *sides) {
     return n;
 }
 
-// The 5-point operator's extreme eigenvalues on an NL x NL Dirichlet grid, and the smallest
-// degree whose Chebyshev error bound 1 / cosh((nu + 1) acosh sigma) is at most 0.1.
-int mg_coarse_degree(int NL, double *lo, double *hi) {
+// The extreme eigenvalues of the 5-point operator plus `shift` (the coarsest level's, 4^L
+// times the context's) on an NL x NL Dirichlet grid, and the smallest degree whose Chebyshev
+// error bound 1 / cosh((nu + 1) acosh sigma) is at most 0.1.
+int mg_coarse_degree(int NL, double shift, double *lo, double *hi) {
     const double pi = 3.14159265358979323846;
     const double t = pi / (2.0 * (NL + 1));
     const double sn = std::sin(t), cs = std::cos(t);
-    *lo = 8.0 * sn * sn;
-    *hi = 8.0 * cs * cs;
+    *lo = 8.0 * sn * sn + shift;
+    *hi = 8.0 * cs * cs + shift;
     const double sigma = (*hi + *lo) / (*hi - *lo);
     const double ac = std::acosh(sigma);
     for (int nu = 1; nu <= MG_CDEG_MAX; ++nu)
@@ -53,6 +54,7 @@ struct MgrArgs {
     const double *x;  // RESID: z ; else f
     const double *r;  // RESID: the right-hand side of the residual
     double *rc;       // coarse output, (N/2)^2
+    double diag;      // RESID: the level's diagonal, fl(4 + shift_l)
     int N, JT;        // fine side (even), lines per workgroup (even)
 };
 
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(TPB) void k_mg_restrict(MgrArgs a) {
             double rv[2], f[2];
             ld_vec<2>(m.act ? a.r + row + m.i0 : nullptr, m.act, rv);
 #pragma unroll
-            for (int k = 0; k < 2; ++k) f[k] = rv[k] - ax5_at<2>(k, tc, tp, tm, left, right);
+            for (int k = 0; k < 2; ++k) f[k] = rv[k] - ax5_at<2>(a.diag, k, tc, tp, tm, left, right);
             if ((j & 1) == 0) {
                 pend = f[0] + f[1];
             } else {
@@ -106,7 +108,8 @@ __global__ __launch_bounds__(TPB) void k_mg_restrict(MgrArgs a) {
     }
 }
 
-hipError_t mg_restrict(bool fused, int N, const double *x, const double *r, double *rc, hipStream_t st) {
+hipError_t mg_restrict(bool fused, int N, double diag, const double *x, const double *r, double *rc,
+                       hipStream_t st) {
     if (N < 2 || (N & 1) || x == nullptr || rc == nullptr || (fused && r == nullptr)) return hipErrorInvalidValue;
     const int gx = (N + TPB * 2 - 1) / (TPB * 2);
     // ~2048 workgroups of at most 64 lines, as set_geometry sizes the stencil sweeps, but an even
@@ -115,7 +118,7 @@ hipError_t mg_restrict(bool fused, int N, const double *x, const double *r, doub
     JT = (JT + 1) & ~1;
     JT = JT < 2 ? 2 : (JT > 64 ? 64 : JT);
     const dim3 g(gx, (N + JT - 1) / JT, 1);
-    MgrArgs a{x, r, rc, N, JT};
+    MgrArgs a{x, r, rc, diag, N, JT};
     if (fused)
         k_mg_restrict<true><<<g, TPB, 0, st>>>(a);
     else

@@ -21,13 +21,15 @@ constexpr int MG_CDEG_MAX = 64; // coarsest-level degree cap (gk_set_precond's C
 
 // Pure host: the level sides into sides[0 .. MG_LMAX) and their count (0: N has no coarse
 // level -- odd, or N / 2 < MG_NMIN), and the coarsest level's exact spectrum interval
-// (lo, hi) and sweep count.
+// (lo, hi), moved by that level's shift, and sweep count.
 GK_HIDDEN int mg_levels(int N, int *sides);
-GK_HIDDEN int mg_coarse_degree(int NL, double *lo, double *hi);
+GK_HIDDEN int mg_coarse_degree(int NL, double shift, double *lo, double *hi);
 
 // Each returns hipGetLastError() of its launch (hipErrorInvalidValue for an odd N).
-// fused: rc = P^T (r - A z), x = z, r = r; else rc = P^T x (r unused).
-GK_HIDDEN hipError_t mg_restrict(bool fused, int N, const double *x, const double *r, double *rc, hipStream_t st);
+// fused: rc = P^T (r - A z), x = z, r = r, A's diagonal diag = fl(4 + shift_l); else rc = P^T x
+// (r, diag unused).
+GK_HIDDEN hipError_t mg_restrict(bool fused, int N, double diag, const double *x, const double *r, double *rc,
+                                 hipStream_t st);
 GK_HIDDEN hipError_t mg_prolong_add(int N, const double *z, const double *ec, double *out, hipStream_t st);
 // G workgroups (<= NPMAX); acc != ACC_NONE: part[b] = workgroup b's partial of <out, vdot> / <out, out>
 GK_HIDDEN hipError_t mg_add(int acc, int G, i64 n, const double *a, const double *b, double *out, const double *vdot,

@@ -40,6 +40,7 @@ int stencil(gk_ctx *c, int op, int acc, gk::StArgs a) {
     if (acc != gk::ACC_NONE) c->last_np = c->np_st;
     a.hlo = halo_lo(c);
     a.hhi = halo_hi(c);
+    a.diag = diag_of(c);
     a.N = c->N;
     a.nlines = c->nlines;
     a.JT = c->JT;
@@ -85,6 +86,7 @@ int stencil_plain_raw(gk_ctx *c, const double *x, const double *hlo, const doubl
     gk::StArgs a{};
     a.x = x;
     a.y = y;
+    a.diag = diag_of(c);
     a.N = c->N;
     a.nlines = c->nlines;
     a.JT = c->JT;
@@ -137,6 +139,7 @@ int right_cbpr2(gk_ctx *c, const double *v, double *out, int acc, const double *
     a.vdot = vdot;
     a.part = part;
     cbpr2_coefs(c, &a.d, &a.alpha);
+    a.diag = diag_of(c);
     a.N = c->N;
     a.nlines = c->nlines;
     a.JT = c->JT;
@@ -190,6 +193,7 @@ int cheb_fused(gk_ctx *c, const double *in, double *out, int acc, const double *
     a.N = c->N;
     a.nlines = c->nlines;
     a.theta = theta;
+    a.diag = diag_of(c);
     a.din = sten ? sten_v : in;
     a.vdot = vdot;
     a.part = part;
@@ -212,6 +216,7 @@ int cheb_fused(gk_ctx *c, const double *in, double *out, int acc, const double *
     gk::CFArgs b{};
     b.N = c->N;
     b.nlines = c->nlines;
+    b.diag = diag_of(c);
     b.din = c->dA;
     b.rin = c->aux;
     b.zin = c->dB;
@@ -325,8 +330,9 @@ int mg_build(gk_ctx *c, double p0, double p1, int degree) {
         mg_free(c);
         return set_err(GK_ERR_HIP, "memset failed");
     }
-    double lo = 0.0, hi = 0.0;
-    c->mg_cdeg = gk::mg_coarse_degree(sides[L], &lo, &hi);
+    c->mg_p0 = p0;
+    c->mg_p1 = p1;
+    c->mg_deg = degree;
     double *p = c->mg_buf;
     auto take = [&](int n) {
         double *q = p;
@@ -351,9 +357,6 @@ int mg_build(gk_ctx *c, double p0, double p1, int degree) {
         lc->res_cus = c->res_cus;
         set_geometry(lc);
         lc->pkind = GK_PREC_CHEB;
-        lc->p0 = l < L ? p0 : lo;
-        lc->p1 = l < L ? p1 : hi;
-        lc->pdeg = l < L ? degree : c->mg_cdeg;
         if (l > 0) {
             lv.r = take(n);
             lv.e = take(n);
@@ -373,7 +376,33 @@ int mg_build(gk_ctx *c, double p0, double p1, int degree) {
             lc->dB = take(n);
         }
     }
+    mg_refresh(c);
     return GK_OK;
+}
+
+// The levels under the context's shift sigma.  Every level runs the same unscaled stencil on
+// a mesh twice as wide, so the shift is rediscretised by the same scaling, exactly:
+// sigma_l = 4^l sigma, diag_l = fl(4 + sigma_l).  (Galerkin: P^T (A + sigma I) P = 2 A_c +
+// 4 sigma I; halving it as for A would leave 2 sigma and over-correct the smooth modes.)
+// The caller's interval is level 0's; level l smooths on it moved by sigma_l - sigma, the
+// coarsest level on its exact interval plus sigma_L with the degree that interval asks for.
+// Host state only: captured graphs hold the old values (gk_set_shift drops them).
+void mg_refresh(gk_ctx *c) {
+    if (c->mg.size() < 2) return;
+    const int L = (int)c->mg.size() - 1;
+    double sl = c->shift;
+    for (int l = 0; l <= L; ++l, sl *= 4.0) {
+        gk_ctx *lc = c->mg[l].lc;
+        lc->shift = sl;
+        if (l < L) {
+            lc->p0 = c->mg_p0 + (sl - c->shift);
+            lc->p1 = c->mg_p1 + (sl - c->shift);
+            lc->pdeg = c->mg_deg;
+        } else {
+            c->mg_cdeg = gk::mg_coarse_degree(lc->N, sl, &lc->p0, &lc->p1);
+            lc->pdeg = c->mg_cdeg;
+        }
+    }
 }
 
 // out = r - A z on level context lc (OP_RESID's expression with in1 = r)
@@ -389,11 +418,11 @@ static int mg_resid(gk_ctx *lc, const double *z, const double *r, double *out) {
 // restriction -- the same expressions in the same order, bit-identical rc.
 static int mg_resid_restrict(gk_ctx *c, gk_mg_level &lv, const double *r, double *rc) {
     if (c->tune_mg_fused) {
-        HIPCHK(gk::mg_restrict(true, lv.lc->N, lv.z, r, rc, c->st));
+        HIPCHK(gk::mg_restrict(true, lv.lc->N, diag_of(lv.lc), lv.z, r, rc, c->st));
         return GK_OK;
     }
     CHK(mg_resid(lv.lc, lv.z, r, lv.t));
-    HIPCHK(gk::mg_restrict(false, lv.lc->N, lv.t, nullptr, rc, c->st));
+    HIPCHK(gk::mg_restrict(false, lv.lc->N, 0.0, lv.t, nullptr, rc, c->st));
     return GK_OK;
 }
 
@@ -446,9 +475,9 @@ int mg_transfer(gk_ctx *c, int what, int level, const double *a, const double *b
     HIPCHK(hipMemcpyAsync(f.t, a, nf, hipMemcpyHostToDevice, c->st));
     if (what == 1) {  // out = P^T (a - A b) by the fused march
         HIPCHK(hipMemcpyAsync(f.z, b, nf, hipMemcpyHostToDevice, c->st));
-        HIPCHK(gk::mg_restrict(true, N, f.z, f.t, g.r, c->st));
+        HIPCHK(gk::mg_restrict(true, N, diag_of(f.lc), f.z, f.t, g.r, c->st));
     } else {  // out = P^T a
-        HIPCHK(gk::mg_restrict(false, N, f.t, nullptr, g.r, c->st));
+        HIPCHK(gk::mg_restrict(false, N, 0.0, f.t, nullptr, g.r, c->st));
     }
     HIPCHK(hipMemcpyAsync(out, g.r, nc, hipMemcpyDeviceToHost, c->st));
     return sync_st(c);

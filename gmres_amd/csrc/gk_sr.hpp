@@ -105,6 +105,7 @@ struct SrArgs {
     double *hist;                   // device history [maxit]
     SrMirror *mir;                  // mapped host mirror
     double cd, ca;                  // cbpr2: d, alpha (chebyshev.f90:19-25)
+    double diag;                    // the operator's diagonal, fl(4 + shift) (gk_march.hpp: ax5)
     int N, nlines, JT, fin;
 };
 
@@ -371,7 +372,7 @@ __global__ __launch_bounds__(TPB) void k_sr_march(SrArgs a) {
             double yv[VEC];
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
-                const double ax = ax5_at<VEC>(k, tc, tp, tm, left, right);
+                const double ax = ax5_at<VEC>(a.diag, k, tc, tp, tm, left, right);
                 if constexpr (CB) {
                     yv[k] = tc[k] + ca * (uc[k] - ax);
                 } else {
@@ -535,7 +536,7 @@ __global__ __launch_bounds__(TPB) void k_sr_march2(SrArgs a) {
         const bool lv = jj >= 0 && jj < nl;
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
-            const double ax = ax5_at<VEC>(k, uc.t, un.t, us.t, left, right);
+            const double ax = ax5_at<VEC>(a.diag, k, uc.t, un.t, us.t, left, right);
             const double v = CG ? rr.v[k] - al * ax : uc.t[k] + ca * (uc.u[k] - ax);
             o.v[k] = (lv && m.act) ? v : 0.0;
             o.t[k] = CG ? o.v[k] / dv : o.v[k];
@@ -543,7 +544,7 @@ __global__ __launch_bounds__(TPB) void k_sr_march2(SrArgs a) {
         // the edge point ea: lane 0 -> W = eb, E = own point 0; lane 63 -> W = own point VEC-1, E = eb
         const double Wa = e.e0 ? uc.tb : uc.t[VEC - 1];
         const double Ea = e.e0 ? uc.t[0] : uc.tb;
-        const double axa = ax5(uc.ta, Wa, Ea, un.ta, us.ta);
+        const double axa = ax5(a.diag, uc.ta, Wa, Ea, un.ta, us.ta);
         const double va = CG ? rr.a - al * axa : uc.ta + ca * (uc.ua - axa);
         o.va = lv ? va : 0.0;
         o.ta = CG ? o.va / dv : o.va;
@@ -596,7 +597,7 @@ __global__ __launch_bounds__(TPB) void k_sr_march2(SrArgs a) {
             double y[VEC];
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
-                const double ax = ax5_at<VEC>(k, vc.t, vp.t, vm.t, left, right);
+                const double ax = ax5_at<VEC>(a.diag, k, vc.t, vp.t, vm.t, left, right);
                 y[k] = CG ? vc.t[k] + ca * (vc.v[k] - ax) : ax;
                 if constexpr (CG) xc[k] = xc[k] + al * u0.u[k];
             }

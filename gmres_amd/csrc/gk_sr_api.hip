@@ -51,6 +51,7 @@ gk::SrArgs sr_args(gk_ctx *c) {
     a.N = c->N;
     a.nlines = c->nlines;
     a.JT = c->sr_JT;
+    a.diag = diag_of(c);
     // cbpr2 coefficients exactly as chebyshev.f90:19-25 (precond_sweeps)
     const double cc = (c->p1 - c->p0) / 2.0, d = (c->p1 + c->p0) / 2.0;
     double al = 1.0 / d;

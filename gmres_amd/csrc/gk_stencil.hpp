@@ -39,6 +39,7 @@ struct StArgs {
     const double *vdot; // ACC_DOT partner vector
     double *part;       // partial slab (ACC != NONE)
     double s1, s2, s3;  // CBPR2: d, alpha ; CHEB: theta(first)/unused, c1, c2
+    double diag;        // the operator's diagonal, fl(4 + shift) (gk_march.hpp: ax5)
     int N, nlines, JT;
 };
 
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(TPB) void k_stencil(StArgs a) {
             double resv[VEC], dnv[VEC];
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
-                const double ax = ax5_at<VEC>(k, tc, tp, tm, left, right);
+                const double ax = ax5_at<VEC>(a.diag, k, tc, tp, tm, left, right);
                 if (OP == OP_PLAIN) {
                     yv[k] = ax;
                 } else if (OP == OP_RESID) {
@@ -167,6 +168,7 @@ struct RcArgs {
     const double *vdot; // ACC_DOT partner vector
     double *part;       // partial slab (ACC_DOT)
     double d, alpha;    // cbpr2 coefficients (chebyshev.f90:19-25)
+    double diag;        // the operator's diagonal, fl(4 + shift)
     int N, nlines, JT;
 };
 
@@ -213,14 +215,14 @@ __global__ __launch_bounds__(TPB) void k_right_cbpr2(RcArgs a) {
         const bool lv = jj >= 0 && jj < nl;
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
-            const double ax = ax5_at<VEC>(k, uc.t, un.t, us.t, left, right);
+            const double ax = ax5_at<VEC>(a.diag, k, uc.t, un.t, us.t, left, right);
             const double z = uc.t[k] + ca * (uc.r[k] - ax);
             o.z[k] = (lv && m.act) ? z : 0.0;
         }
         // the edge point ea: lane 0 -> W = eb, E = own point 0; lane 63 -> W = own point VEC-1, E = eb
         const double Wa = e.e0 ? uc.tb : uc.t[VEC - 1];
         const double Ea = e.e0 ? uc.t[0] : uc.tb;
-        const double axa = ax5(uc.ta, Wa, Ea, un.ta, us.ta);
+        const double axa = ax5(a.diag, uc.ta, Wa, Ea, un.ta, us.ta);
         const double za = uc.ta + ca * (uc.ra - axa);
         o.za = lv ? za : 0.0;
     };
@@ -266,7 +268,7 @@ __global__ __launch_bounds__(TPB) void k_right_cbpr2(RcArgs a) {
             we_select<VEC>(m, e, N, zc.z, zc.za, left, right);
             double yv[VEC];
 #pragma unroll
-            for (int k = 0; k < VEC; ++k) yv[k] = ax5_at<VEC>(k, zc.z, zp.z, zm.z, left, right);
+            for (int k = 0; k < VEC; ++k) yv[k] = ax5_at<VEC>(a.diag, k, zc.z, zp.z, zm.z, left, right);
             if (m.act) {
                 st_vec<VEC>(a.w + row + m.i0, yv);
                 if (ACC == ACC_DOT) {

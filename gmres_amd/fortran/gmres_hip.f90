@@ -61,6 +61,11 @@ module gmres_hip_c
             type(c_ptr), value :: ctx
             integer(c_int), value :: side
         end function
+        integer(c_int) function gk_set_shift(ctx, sigma) bind(C, name='gk_set_shift')
+            import :: c_int, c_ptr, c_double
+            type(c_ptr), value :: ctx
+            real(c_double), value :: sigma
+        end function
         integer(c_int) function gk_set_basis_precision(ctx, prec) bind(C, name='gk_set_basis_precision')
             import :: c_ptr, c_int
             type(c_ptr), value :: ctx
@@ -325,7 +330,7 @@ module gmres_hip
     public :: GK_SIDE_LEFT, GK_SIDE_RIGHT, GK_BASIS_F64, GK_BASIS_F32, GK_ORTH_MGSR, GK_ORTH_CGS2
     public :: GK_HH_PREC_NONE, GK_HH_PREC_LEFT, GK_HH_PREC_RIGHT
     public :: hip_poisson5, hip_identity, hip_cbpr2, hip_chebyshev, hip_mg
-    public :: gmres_mgsr_hip, gmres_hh_hip, gmres_hh_prec_hip, hip_release
+    public :: gmres_mgsr_hip, gmres_hh_hip, gmres_hh_prec_hip, hip_release, hip_set_shift
     public :: pcg_hip, pbicgstab_hip, pcg_drive, bicgstab_drive, pcg_drive_seq, bicgstab_drive_seq
     !> iterations queued per chunk by the fused short-recurrence drivers
     integer, public :: hip_sr_chunk = 32
@@ -333,6 +338,7 @@ module gmres_hip
 
     type(c_ptr) :: opctx = c_null_ptr   ! context of the host-array plug-ins
     integer :: opctx_n = -1
+    real(8) :: shift_sigma = 0.0d0      ! hip_set_shift: the operator is A_poisson + shift_sigma I
 contains
 
     ! ------------------------------------------------------------- helpers --
@@ -766,8 +772,22 @@ contains
         if (c_associated(opctx)) call gk_require(gk_destroy(opctx), 'gk_destroy')
         call gk_require(gk_create(int(hip_device, c_int), int(n, c_int), 0_c_int, int(n, c_int), 1_c_int, opctx), &
                         'gk_create')
+        call gk_require(gk_set_shift(opctx, shift_sigma), 'gk_set_shift')
         opctx_n = n
     end subroutine ensure_opctx
+
+    !> The operator of everything below becomes A_poisson + sigma I, sigma >= 0
+    !> (include/gmres_hip.h gk_set_shift): y = fma(fl(4 + sigma), c, -s) at every point;
+    !> hip_mg runs level l with sigma_l = 4^l sigma and smooths on [params(1), params(2)]
+    !> moved by sigma_l - sigma.  params of hip_cbpr2 / hip_chebyshev / hip_mg are the
+    !> interval of the shifted operator.  Module state: it applies to hip_poisson5 and the
+    !> hip_* preconditioner plug-ins from this call on and to every context the five drop-in
+    !> solvers create; for time stepping set it once and pass a new b per step.
+    subroutine hip_set_shift(sigma)
+        real(8), intent(in) :: sigma
+        if (c_associated(opctx)) call gk_require(gk_set_shift(opctx, sigma), 'gk_set_shift')
+        shift_sigma = sigma
+    end subroutine hip_set_shift
 
     !> Free the plug-ins' device context.
     subroutine hip_release()
@@ -912,6 +932,7 @@ contains
         if (size(params) >= 2) p = params(1:2)
         call gk_require(gk_create(int(hip_device, c_int), int(nsize, c_int), 0_c_int, int(nsize, c_int), &
                                   int(m, c_int), ctx), 'gk_create')
+        call gk_require(gk_set_shift(ctx, shift_sigma), 'gk_set_shift')
         call gk_require(gk_set_precond(ctx, kind, p, 2_c_int, degree), 'gk_set_precond')
         call gk_require(gk_set_precond_side(ctx, sd), 'gk_set_precond_side')
         call gk_require(gk_set_rhs(ctx, b), 'gk_set_rhs')

@@ -11,27 +11,31 @@
 !! `hhright` runs the Householder solve alone, preconditioned on the
 !! right (gmres_hh_prec_hip(..., side = GK_SIDE_RIGHT)), and prints its final residual
 !! a second time with every digit; `mg` runs the MGS-R solve alone with the multigrid
-!! V-cycle hip_mg on the right (smoother interval (8, 1), tol 1e-12), then pcg_hip with it.
+!! V-cycle hip_mg on the right (smoother interval (8, 1), tol 1e-12), then pcg_hip with it;
+!! `shift` runs those two legs on the shifted operator A + 0.5 I (hip_set_shift(0.5):
+!! b = (A + 0.5 I)*1 through hip_poisson5, smoother interval (8.5, 1.5)).
 program test_mfp_hip
     use gmres_hip
     implicit none
     integer :: nsize, max_iter, n_args
     character(len=32) :: arg_str
-    logical :: right, f32, hhright, cgs2, mg
+    logical :: right, f32, hhright, cgs2, mg, shifted
     n_args = command_argument_count()
     if (n_args < 2) then
-        print *, "usage ./test_mfp_hip <grid size> <iterations per restart> [right|f32|cgs2|hhright|mg]"
+        print *, "usage ./test_mfp_hip <grid size> <iterations per restart> [right|f32|cgs2|shift|hhright|mg]"
         stop
     end if
-    right = .false.; f32 = .false.; hhright = .false.; cgs2 = .false.; mg = .false.
+    right = .false.; f32 = .false.; hhright = .false.; cgs2 = .false.; mg = .false.; shifted = .false.
     if (n_args >= 3) then
         call get_command_argument(3, arg_str)
         right = trim(arg_str) == 'right'
         f32 = trim(arg_str) == 'f32'
         cgs2 = trim(arg_str) == 'cgs2'
         hhright = trim(arg_str) == 'hhright'
-        mg = trim(arg_str) == 'mg'
+        shifted = trim(arg_str) == 'shift'
+        mg = trim(arg_str) == 'mg' .or. shifted
     end if
+    if (shifted) call hip_set_shift(0.5d0)
     call get_command_argument(1, arg_str)
     read (arg_str, *) nsize
     call get_command_argument(2, arg_str)
@@ -58,10 +62,15 @@ contains
         integer :: iter
         allocate (b(nsize*nsize), x(nsize*nsize))
         params = [8.0d0, 1.0d0]
+        if (shifted) params = [8.5d0, 1.5d0]
         x = 1.0d0
         call hip_poisson5(x, b, nsize)
         iter = 200
-        write (*, '(A)') 'PCG Poisson 2D Test Matrix Free (multigrid V-cycle, MI355X)'
+        if (shifted) then
+            write (*, '(A)') 'PCG Poisson 2D Test Matrix Free (shifted A + 0.5 I, multigrid V-cycle, MI355X)'
+        else
+            write (*, '(A)') 'PCG Poisson 2D Test Matrix Free (multigrid V-cycle, MI355X)'
+        end if
         call pcg_hip(hip_poisson5, b, x, 1.d-10, iter, res, hip_mg, params)
         write (*, '(A30, I8)') 'PCG iterations:', iter
         write (*, '(A30, ES12.4)') 'PCG residual:', res
@@ -80,6 +89,9 @@ contains
         if (mg) then
             tol = 1.d-12
             params(1) = 8.0d0; params(2) = 1.0d0
+            if (shifted) then
+                params(1) = 8.5d0; params(2) = 1.5d0
+            end if
         end if
         x = 1.0d0
         call hip_poisson5(x, b, nsize)   ! b = A*1: every solution entry must be 1.0
@@ -93,6 +105,8 @@ contains
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR Chebyshev, compressed basis, MI355X)'
         else if (cgs2) then
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (CGS2 Chebyshev, MI355X)'
+        else if (shifted) then
+            write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (shifted A + 0.5 I, MGSR multigrid V-cycle on the right, MI355X)'
         else if (mg) then
             write (*, '(A)') 'GMRES Poisson 2D Test Matrix Free (MGSR multigrid V-cycle on the right, MI355X)'
         else

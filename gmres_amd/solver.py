@@ -212,6 +212,21 @@ class Context:
             nat.check(nat.hip().gk_set_precond_side(self._h, SIDE[side]), "gk_set_precond_side")
             self.side = side
 
+    def set_shift(self, sigma: float) -> None:
+        """The operator becomes A_poisson + sigma I, sigma >= 0 (gk_set_shift): one fused
+        y = fma(fl(4 + sigma), c, -s) on every path; multigrid level l runs sigma_l = 4^l sigma
+        and smooths on the caller's interval moved by sigma_l - sigma.  params of cbpr2 /
+        Chebyshev stay the caller's interval, now that of the shifted operator.  Ends an open
+        cycle and a running short-recurrence solve; b and x are untouched (set_rhs_ones after
+        it gives b = (A + sigma I) 1)."""
+        nat.check(nat.hip().gk_set_shift(self._h, float(sigma)), "gk_set_shift")
+
+    @property
+    def shift(self) -> float:
+        v = ctypes.c_double()
+        nat.check(nat.hip().gk_get_shift(self._h, ctypes.byref(v)), "gk_get_shift")
+        return v.value
+
     def set_basis(self, basis: str = "f64") -> None:
         """Storage precision of the MGS-R Krylov columns (gk_set_basis_precision): "f64"
         (default) or "f32", the compressed basis -- columns stored as FP32, all arithmetic
@@ -594,8 +609,16 @@ def _stream_handle(stream) -> int:
     return int(stream.cuda_stream) if stream is not None else 0
 
 
-def poisson5(x, y, N: int, nlines: int | None = None, halo_lo=None, halo_hi=None, stream=None) -> None:
+def poisson5(x, y, N: int, nlines: int | None = None, halo_lo=None, halo_hi=None, stream=None,
+             shift: float = 0.0) -> None:
+    """y = (A + shift I) x on a slab; shift 0 (the default) is gk_poisson5 itself."""
     nl = N if nlines is None else nlines
+    if shift != 0.0:
+        nat.check(nat.hip().gk_poisson5_shift(N, nl, float(shift), x.data_ptr(),
+                                              halo_lo.data_ptr() if halo_lo is not None else None,
+                                              halo_hi.data_ptr() if halo_hi is not None else None, y.data_ptr(),
+                                              _stream_handle(stream)), "gk_poisson5_shift")
+        return
     nat.check(nat.hip().gk_poisson5(N, nl, x.data_ptr(), halo_lo.data_ptr() if halo_lo is not None else None,
                                     halo_hi.data_ptr() if halo_hi is not None else None, y.data_ptr(),
                                     _stream_handle(stream)), "gk_poisson5")

@@ -216,6 +216,30 @@ int gk_mg_transfer(gk_ctx *ctx, int what, int level, const double *a, const doub
 #define GK_SIDE_LEFT 0
 #define GK_SIDE_RIGHT 1
 int gk_set_precond_side(gk_ctx *ctx, int side);
+/* The operator's shift (context state; default 0): A := A_poisson + sigma I, sigma >= 0 --
+ * implicit diffusion steps (I + tau (-Laplace)), screened Poisson, pseudo-time continuation,
+ * after scaling.  One rule everywhere: with s = ((W + E) + N) + S in the stencil's order,
+ *   y = fma(diag, c, -s),  diag = fl(4 + sigma),
+ * ONE fused multiply-add on every path (stencil sweeps, cbpr2 marches, the Chebyshev passes,
+ * the short-recurrence marches, the multigrid residuals); at sigma = 0 it is bit-identical to
+ * 4 c - s.  A stays symmetric positive definite, so every solver and preconditioner applies.
+ *   cbpr2 / Chebyshev: params are the caller's interval as before, now that of A + sigma I
+ *     (e.g. (8.2 + sigma, 0.2 + sigma)); nothing is added for the caller.
+ *   GK_PREC_MG: level l runs the same stencil with sigma_l = 4^l sigma (the shift
+ *     rediscretised as the operator is; Galerkin's 4 sigma, not its half), diag_l =
+ *     fl(4 + sigma_l).  params are level 0's interval; level l smooths on it moved by
+ *     sigma_l - sigma; the last level on its exact interval plus sigma_L, with nu_c recomputed
+ *     from that interval (gk_mg_info reports it).  Setting the shift refreshes a live hierarchy
+ *     in place (no allocation); gk_set_precond(MG) after it builds by the same rule.
+ * Setting the shift ends a running gk_sr_* solve and an open GMRES cycle (as
+ * gk_set_precond_side does) and, when the value changes, drops the captured step graphs,
+ * which hold diag by value.  b and x are not touched: gk_set_rhs_ones after gk_set_shift
+ * gives b = (A + sigma I) 1.  No device allocation, no synchronisation of its own.  On N
+ * ranks every rank sets the same value (not checked, like params); halos and collectives
+ * are unaffected.  GK_ERR_ARG: sigma < 0, not finite, or > 1e12 (4^l sigma stays finite).
+ * gk_poisson5, gk_precond_apply and gk_mg_plan_query keep meaning sigma = 0. */
+int gk_set_shift(gk_ctx *ctx, double sigma);
+int gk_get_shift(gk_ctx *ctx, double *sigma);
 /* Storage precision of the Krylov basis in the MGS-R cycle (context state; default
  * GK_BASIS_F64; beyond the reference).
  *   GK_BASIS_F64  every column an FP64 vector (the reference).
@@ -296,7 +320,8 @@ int gk_cb_plan_query(long long nloc, int cus, int share, int m, long long *info)
 int gk_set_orthogonalization(gk_ctx *ctx, int scheme);
 int gk_get_orthogonalization(gk_ctx *ctx, int *scheme);
 /* Right-hand side b (local part, host) or b = A*1 built on device
- * (the manufactured RHS of every reference driver, test_poisson_mf.f90:39-40). */
+ * (the manufactured RHS of every reference driver, test_poisson_mf.f90:39-40).
+ * A is the shifted operator: for b = (A + sigma I) 1 call gk_set_shift first. */
 int gk_set_rhs(gk_ctx *ctx, const double *b_local);
 int gk_set_rhs_ones(gk_ctx *ctx);
 /* beta0 = ||b||_2 (global). */
@@ -328,7 +353,8 @@ int gk_set_basis(gk_ctx *ctx, int col, const double *in);
 int gk_set_x(gk_ctx *ctx, const double *x_local);
 /* Host-array operator application on this context's slab (clobbers the
  * work vectors; not between cycle start and update):  what = 0: out = A in
- * (stencil_vector, poisson.f90:33-77); what = 1: out = M^-1 in (precond). */
+ * (stencil_vector, poisson.f90:33-77); what = 1: out = M^-1 in (precond).
+ * A is A_poisson + sigma I (gk_set_shift), here and in gk_true_residual. */
 int gk_apply(gk_ctx *ctx, int what, const double *in, double *out);
 /* ||b - A x|| / ||b|| (global, true unpreconditioned residual). */
 int gk_true_residual(gk_ctx *ctx, double *rel);
@@ -403,7 +429,9 @@ int gk_hh_verr(gk_ctx *ctx, int n_out, double *v_err);
  * same for any slab decomposition); returns the extreme Ritz values of the
  * k x k tridiagonal (Sturm bisection on the host).  The README-promised
  * eigenvalue estimate for the Chebyshev parameters (README.md:11; the
- * reference hard-codes params, chebyshev.f90:20).  Clobbers work vectors. */
+ * reference hard-codes params, chebyshev.f90:20).  Clobbers work vectors.
+ * A is A_poisson + sigma I (gk_set_shift): the bounds are those at sigma = 0
+ * plus sigma (the same Krylov space). */
 int gk_lanczos_bounds(gk_ctx *ctx, int k, double *lmin, double *lmax);
 
 /* ------------------------------------------- device vector primitives ---- */
@@ -422,7 +450,7 @@ int gk_lanczos_bounds(gk_ctx *ctx, int k, double *lmin, double *lmax);
 int gk_vec_count(gk_ctx *ctx, int *count);
 /* what = 0: out = A in; what = 1: out = M^-1 in; what = 2: out = A M^-1 in, the
  * operator of a right-preconditioned step by the step's own route (whatever the
- * context's side is); in != out. */
+ * context's side is); in != out.  A is A_poisson + sigma I (gk_set_shift). */
 int gk_vec_apply(gk_ctx *ctx, int what, int in, int out);
 /* result = <a, b> over all ranks (synchronous). */
 int gk_vec_dot(gk_ctx *ctx, int a, int b, double *result);
@@ -716,6 +744,10 @@ int gk_debug_hold_stream(gk_ctx *ctx, int hold);
  * -- stencil_vector, src/problems/poisson.f90:33-77.  stream: hipStream_t. */
 int gk_poisson5(int nside, int nlines, const double *x, const double *halo_lo,
                 const double *halo_hi, double *y, void *stream);
+/* ... and y = (A + sigma I) x by gk_set_shift's rule, y = fma(fl(4 + sigma), c, -s);
+ * GK_ERR_ARG for sigma < 0, not finite or > 1e12.  gk_poisson5 is sigma = 0. */
+int gk_poisson5_shift(int nside, int nlines, double sigma, const double *x, const double *halo_lo,
+                      const double *halo_hi, double *y, void *stream);
 /* z = M^-1 r for the single-slab case (precond, src/interfaces.f90:20-27);
  * scratch: 3 vectors of N*N doubles. */
 int gk_precond_apply(int nside, int kind, const double *params, int degree, const double *r,

@@ -25,6 +25,10 @@ profiles/mg/mg_bench_<grid>.jsonl; --append adds a run, e.g. a second m, to it).
 
   python tools/mg_bench.py [--grid 4096] [--m 95] [--samples 3] [--baseline-samples 1]
   python tools/mg_bench.py --grid 4096 --m 30 --max-cycles 60 --append
+
+--shift SIGMA runs every leg on A + SIGMA I (gk_set_shift; b = (A + SIGMA I) 1, every interval
+moved by SIGMA: the multigrid smoother's (8 + SIGMA, 1 + SIGMA), the others' (8.2 + SIGMA,
+0.2 + SIGMA)); its records carry "shift".
 """
 import argparse
 import json
@@ -57,6 +61,7 @@ def main() -> None:
     ap.add_argument("--baseline-samples", type=int, default=1)
     ap.add_argument("--max-cycles", type=int, default=20)
     ap.add_argument("--max-iter", type=int, default=3000)
+    ap.add_argument("--shift", type=float, default=0.0, help="the operator is A + SHIFT I (default 0)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--append", action="store_true", help="append to --out instead of rewriting it")
     a = ap.parse_args()
@@ -75,16 +80,19 @@ def main() -> None:
 
     m, n = a.m, a.grid * a.grid
     base = {"grid": a.grid, "m": m, "tol": TOL}
+    sg = a.shift
+    if sg != 0.0:
+        base["shift"] = sg
     ctxs = {}
 
     def configure(c, leg, side):
         if leg in MG_LEGS:
             c.tune(nat.GK_TUNE_MG_FUSED, 1 if leg == "mg" else 0)
-            c.set_precond("mg", side=side)
+            c.set_precond("mg", (8.0 + sg, 1.0 + sg) if sg != 0.0 else None, side=side)
         elif leg == "cheb8":
-            c.set_precond("cheb", (8.2, 0.2), 8, side=side)
+            c.set_precond("cheb", (8.2 + sg, 0.2 + sg), 8, side=side)
         else:
-            c.set_precond("cbpr2", (8.2, 0.2), side=side)
+            c.set_precond("cbpr2", (8.2 + sg, 0.2 + sg), side=side)
 
     def solve_gmres(c, cycles):
         t0 = time.perf_counter()
@@ -102,6 +110,8 @@ def main() -> None:
     try:
         for leg in LEGS:
             c = ctxs[leg] = ga.Context(a.grid, m)
+            if sg != 0.0:
+                c.set_shift(sg)
             c.set_rhs_ones()
             c.beta = c.rhs_norm()
         for solver, side, solve, cap, warm in (("mgsr_right", "right", solve_gmres, a.max_cycles, 1),
