@@ -79,7 +79,7 @@ void graph_reset(gk_ctx *c) {
 }
 
 // -------------------------------------------------------------- geometry ---
-void set_geometry(gk_ctx *c) {
+void set_geometry(gk_grid *c) {
     const int N = c->N;
     c->vec = (N % 2 == 0) ? 2 : 1;
     const int gx = (N + gk::TPB * c->vec - 1) / (gk::TPB * c->vec);
@@ -173,6 +173,7 @@ int gk_create(int device, int nside, int line0, int nlines, int m, gk_ctx **out)
     }
     HIPCHK(hipSetDevice(device));
     gk_ctx *c = new gk_ctx();
+    c->ctx = c;
     c->cgs_kb = cgs_kb;
     c->dev = device;
     c->N = nside;
@@ -303,13 +304,21 @@ int gk_local_size(gk_ctx *c, long long *nloc) {
     return GK_OK;
 }
 
-int gk_set_precond(gk_ctx *c, int kind, const double *params, int nparams, int degree) {
-    CHK(check_ctx(c));
-    sr_invalidate(c);
+// What gk_set_precond and gk_precond_apply refuse of (kind, params, degree) alone
+static int check_precond_args(int kind, const double *params, int nparams, int degree) {
     if (kind < GK_PREC_IDENTITY || kind > GK_PREC_MG) return set_err(GK_ERR_ARG, "bad precond kind %d", kind);
     if (kind != GK_PREC_IDENTITY && (params == nullptr || nparams < 2))
         return set_err(GK_ERR_ARG, "precond needs params(1:2)");
     if (kind == GK_PREC_CHEB && (degree < 1 || degree > 64)) return set_err(GK_ERR_ARG, "bad degree %d", degree);
+    if (kind == GK_PREC_CHEB && std::fabs(params[1] - params[0]) == 0.0)
+        return set_err(GK_ERR_ARG, "Chebyshev interval is empty");
+    return GK_OK;
+}
+
+int gk_set_precond(gk_ctx *c, int kind, const double *params, int nparams, int degree) {
+    CHK(check_ctx(c));
+    sr_invalidate(c);
+    CHK(check_precond_args(kind, params, nparams, degree));
     if (kind == GK_PREC_MG) {  // everything checked, and the hierarchy built, before the context changes
         int sides[gk::MG_LMAX];
         if (gk::mg_levels(c->N, sides) < 2)
@@ -319,7 +328,6 @@ int gk_set_precond(gk_ctx *c, int kind, const double *params, int nparams, int d
         if (std::fabs(params[1] - params[0]) == 0.0) return set_err(GK_ERR_ARG, "multigrid smoother interval is empty");
         if (c->nranks > 1 || c->comm != nullptr || c->lg != nullptr || c->xs_on || c->line0 != 0 || c->nlines != c->N)
             return set_err(GK_ERR_STATE, "multigrid needs the whole grid on one rank (no communicator)");
-        if (c->V == nullptr) return set_err(GK_ERR_ARG, "multigrid needs a context (gk_create)");
         HIPCHK(hipSetDevice(c->dev));
         // the same cycle again (the host-array plug-in sets it per application): keep the hierarchy
         const bool same = c->pkind == GK_PREC_MG && c->mg.size() >= 2 && c->p0 == params[0] && c->p1 == params[1] &&
@@ -335,8 +343,6 @@ int gk_set_precond(gk_ctx *c, int kind, const double *params, int nparams, int d
     }
     c->pdeg = degree;
     graph_reset(c);
-    if (kind == GK_PREC_CHEB && std::fabs(c->p1 - c->p0) == 0.0)
-        return set_err(GK_ERR_ARG, "Chebyshev interval is empty");
     return GK_OK;
 }
 
@@ -822,7 +828,7 @@ int gk_mg_info(gk_ctx *c, int *info) {
     if (c->pkind != GK_PREC_MG || c->mg.size() < 2) return set_err(GK_ERR_STATE, "no multigrid preconditioner set");
     int sides[gk::MG_LMAX];
     const int nl = (int)c->mg.size();
-    for (int l = 0; l < nl; ++l) sides[l] = c->mg[l].lc->N;
+    for (int l = 0; l < nl; ++l) sides[l] = c->mg[l].g.N;
     mg_info_fill(sides, nl, c->mg_cdeg, c->pdeg, info);
     return GK_OK;
 }
@@ -882,7 +888,8 @@ namespace gkh __attribute__((visibility("hidden"))) {
 // Device scratch for the stateless calls: NSLOT partial slabs + a scalar area.
 double *g_scratch[64] = {nullptr};
 
-int stateless_ctx(gk_ctx &c, int N, int nlines, i64 n, void *stream) {
+// The bare grid of a stateless call: nothing owned, the caller's stream
+int stateless_grid(gk_grid &c, int N, int nlines, i64 n, void *stream) {
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) return set_err(GK_ERR_ARG, "device id %d", dev);
@@ -902,13 +909,6 @@ int stateless_ctx(gk_ctx &c, int N, int nlines, i64 n, void *stream) {
     return GK_OK;
 }
 
-void release_stateless(gk_ctx &c) {
-    // nothing owned: keep the destructor-free fields from being freed
-    c.red = nullptr;
-    c.scal = nullptr;
-    c.st = nullptr;
-}
-
 bool aligned16(const void *p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 }  // namespace gkh
 
@@ -920,12 +920,10 @@ int gk_poisson5_shift(int nside, int nlines, double sigma, const double *x, cons
     if (!(sigma >= 0.0) || !(sigma <= 1e12)) return set_err(GK_ERR_ARG, "shift %g outside 0 .. 1e12", sigma);
     if (!aligned16(x) || !aligned16(y) || !aligned16(hlo) || !aligned16(hhi))
         return set_err(GK_ERR_ARG, "device pointers must be 16-byte aligned");
-    gk_ctx c;
-    CHK(stateless_ctx(c, nside, nlines, (i64)nside * nlines, stream));
+    gk_grid c;
+    CHK(stateless_grid(c, nside, nlines, (i64)nside * nlines, stream));
     c.shift = sigma;
-    const int rc = stencil_plain_raw(&c, x, hlo, hhi, y);
-    release_stateless(c);
-    return rc;
+    return stencil_plain_raw(&c, x, hlo, hhi, y);
 }
 
 int gk_poisson5(int nside, int nlines, const double *x, const double *hlo, const double *hhi, double *y,
@@ -940,46 +938,41 @@ int gk_precond_apply(int nside, int kind, const double *params, int degree, cons
     if (!aligned16(r) || !aligned16(z) || !aligned16(scratch))
         return set_err(GK_ERR_ARG, "device pointers must be 16-byte aligned");
     const i64 n = (i64)nside * nside;
-    gk_ctx c;
-    CHK(stateless_ctx(c, nside, nside, n, stream));
-    int rc = gk_set_precond(&c, kind, params, params ? 2 : 0, degree);
-    if (rc == GK_OK && scratch == nullptr && kind == GK_PREC_CHEB)
-        rc = set_err(GK_ERR_ARG, "Chebyshev needs 3 scratch vectors");
-    if (rc == GK_OK) {
-        // op_precond expects z = A v already formed for a step; here the input
-        // IS the residual, so run the preconditioner sweeps directly on r.
-        c.aux = scratch;
-        c.dA = scratch ? scratch + n : nullptr;
-        c.dB = scratch ? scratch + 2 * n : nullptr;
-        rc = op_Minv_or_copy(&c, r, z);
+    gk_grid c;
+    CHK(stateless_grid(c, nside, nside, n, stream));
+    CHK(check_precond_args(kind, params, params ? 2 : 0, degree));
+    if (scratch == nullptr && kind == GK_PREC_CHEB) return set_err(GK_ERR_ARG, "Chebyshev needs 3 scratch vectors");
+    c.pkind = kind;
+    if (params != nullptr) {
+        c.p0 = params[0];
+        c.p1 = params[1];
     }
-    c.aux = c.dA = c.dB = nullptr;
-    release_stateless(c);
-    return rc;
+    c.pdeg = degree;
+    // op_precond expects z = A v already formed for a step; here the input
+    // IS the residual, so run the preconditioner sweeps directly on r.
+    c.aux = scratch;
+    c.dA = scratch ? scratch + n : nullptr;
+    c.dB = scratch ? scratch + 2 * n : nullptr;
+    return grid_Minv_or_copy(&c, r, z);
 }
 
 int gk_mgs_project(long long n, double *w, const double *va, double *result, void *stream) {
     if (n < 1 || w == nullptr || va == nullptr || result == nullptr) return set_err(GK_ERR_ARG, "bad args");
     if (!aligned16(w) || !aligned16(va)) return set_err(GK_ERR_ARG, "device pointers must be 16-byte aligned");
-    gk_ctx c;
-    CHK(stateless_ctx(c, 2, 1, n, stream));
-    int rc = GK_OK;
-    if (hipMemsetAsync(result, 0, sizeof(double), c.st) != hipSuccess) rc = set_err(GK_ERR_HIP, "memset");
-    if (rc == GK_OK) rc = proj(&c, gk::PJ_DOT, w, nullptr, va, nullptr, 0, slot(&c, 0), nullptr, 1.0);
-    if (rc == GK_OK) rc = proj(&c, gk::PJ_AXPY, w, va, nullptr, slot(&c, 0), c.np_pj, nullptr, result, 1.0);
-    release_stateless(c);
-    return rc;
+    gk_grid c;
+    CHK(stateless_grid(c, 2, 1, n, stream));
+    if (hipMemsetAsync(result, 0, sizeof(double), c.st) != hipSuccess) return set_err(GK_ERR_HIP, "memset");
+    CHK(proj(&c, gk::PJ_DOT, w, nullptr, va, nullptr, 0, slot(&c, 0), nullptr, 1.0));
+    return proj(&c, gk::PJ_AXPY, w, va, nullptr, slot(&c, 0), c.np_pj, nullptr, result, 1.0);
 }
 
 int gk_dot(long long n, const double *a, const double *b, double *result, void *stream) {
     if (n < 1 || a == nullptr || b == nullptr || result == nullptr) return set_err(GK_ERR_ARG, "bad args");
     if (!aligned16(a) || !aligned16(b)) return set_err(GK_ERR_ARG, "device pointers must be 16-byte aligned");
-    gk_ctx c;
-    CHK(stateless_ctx(c, 2, 1, n, stream));
-    int rc = proj(&c, gk::PJ_DOT, const_cast<double *>(a), nullptr, b, nullptr, 0, slot(&c, 0), nullptr, 1.0);
-    if (rc == GK_OK) rc = finalize(&c, slot(&c, 0), c.np_pj, result, 0);
-    release_stateless(c);
-    return rc;
+    gk_grid c;
+    CHK(stateless_grid(c, 2, 1, n, stream));
+    CHK(proj(&c, gk::PJ_DOT, const_cast<double *>(a), nullptr, b, nullptr, 0, slot(&c, 0), nullptr, 1.0));
+    return finalize(&c, slot(&c, 0), c.np_pj, result, 0);
 }
 
 }  // extern "C"

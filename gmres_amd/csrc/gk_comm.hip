@@ -161,8 +161,11 @@ __global__ void k_sum_ranks(RankPtrs src, int nr, double *__restrict__ out, int 
 
 namespace gkh __attribute__((visibility("hidden"))) {
 
-// Collectives run whenever a communicator exists (also a 1-rank RCCL one).
-bool collective(const gk_ctx *c) { return c->xs_on || c->comm != nullptr || c->lg != nullptr; }
+// Collectives run whenever a communicator exists (also a 1-rank RCCL one); a bare grid has none.
+bool collective(const gk_grid *g) {
+    const gk_ctx *c = g->ctx;
+    return c != nullptr && (c->xs_on || c->comm != nullptr || c->lg != nullptr);
+}
 
 // ------------------------------------------------ device exchange (xgmi) ---
 void xs_set_timeout(gk_ctx *c, int ms) {
@@ -403,8 +406,9 @@ int bcast(gk_ctx *c, double *buf, int count, int root) {
 // lines of rank-1 (our rows -nl..-1), hi <- the first nl lines of rank+1 (our
 // rows nlines..nlines+nl-1).  nl = 1 for a stencil sweep; the temporal-blocked
 // Chebyshev passes need nl = L (their recompute cone).
-int halo_lines(gk_ctx *c, const double *vec, int nl, double *lo, double *hi) {
-    if (!collective(c)) return GK_OK;
+int halo_lines(gk_grid *g, const double *vec, int nl, double *lo, double *hi) {
+    if (!collective(g)) return GK_OK;
+    gk_ctx *c = g->ctx;
     // a slab thinner than the halo would send lines it does not own (and its
     // neighbours would need lines from two ranks away)
     if (c->nranks > 1 && (nl < 1 || nl > c->nlines))
@@ -451,10 +455,20 @@ int halo_lines(gk_ctx *c, const double *vec, int nl, double *lo, double *hi) {
     return GK_OK;
 }
 
-int halo(gk_ctx *c, const double *vec) { return halo_lines(c, vec, 1, c->hlo, c->hhi); }
+int halo(gk_grid *g, const double *vec) {
+    gk_ctx *c = g->ctx;
+    return c != nullptr ? halo_lines(g, vec, 1, c->hlo, c->hhi) : GK_OK;
+}
 
-const double *halo_lo(gk_ctx *c) { return (c->nranks > 1 && c->rank > 0) ? c->hlo : nullptr; }
-const double *halo_hi(gk_ctx *c) { return (c->nranks > 1 && c->rank < c->nranks - 1) ? c->hhi : nullptr; }
+// The neighbours' lines halo() received, null at a physical boundary (a bare grid has two)
+const double *halo_lo(const gk_grid *g) {
+    const gk_ctx *c = g->ctx;
+    return (c != nullptr && c->nranks > 1 && c->rank > 0) ? c->hlo : nullptr;
+}
+const double *halo_hi(const gk_grid *g) {
+    const gk_ctx *c = g->ctx;
+    return (c != nullptr && c->nranks > 1 && c->rank < c->nranks - 1) ? c->hhi : nullptr;
+}
 
 }  // namespace gkh
 

@@ -38,31 +38,61 @@ struct gk_group {
     std::vector<const double *> ptrs;
 };
 
-// One level of the GK_PREC_MG hierarchy (gk_op.hip: mg_build / mg_apply / mg_free).  lc is a
-// light context -- the level's side, the parent's device and stream, set_geometry and the
-// level's Chebyshev smoother -- that the stencil and the sweeps run on; the vectors are
-// carved from the parent's mg_buf (level 0 smooths on the parent's aux, dA, dB).
+// One slab of grid lines and all that the operator, the preconditioner sweeps and the
+// streaming launches read of it: everything that takes a gk_grid * (set_geometry, stencil,
+// grid_sweeps, cheb_fused, proj, finalize, ...) runs on these members alone.  A bare grid --
+// a multigrid level, a stateless call's stack object -- owns nothing and has ctx null: no
+// neighbour (halo and collective do nothing, the boundary halos are null) and no profiling
+// events.  A context (gk_ctx) is a grid whose ctx points at itself.
+struct gk_grid {
+    gk_ctx *ctx = nullptr;  // the context this grid is the base of: its communicators and profiling events
+    int dev = 0, N = 0, line0 = 0, nlines = 0;
+    int max_lines = 0;  // largest slab of any rank (0: nlines)
+    i64 nloc = 0, ld = 0, g0 = 0;
+    hipStream_t st = nullptr;
+    // launch geometry (set_geometry) and the tunings it reads
+    int vec = 2, JT = 16;
+    dim3 sgrid;
+    int sr_JT = 64;  // the short-recurrence marches' geometry (gk_sr_*)
+    dim3 sr_sgrid;
+    int np_sr = 0;
+    int np_st = 0, np_pj = 0, nblk_stream = 0;
+    bool nt_auto = false;
+    int tune_nt = -1, tune_pj_blocks = 0, tune_st_blocks = 0, tune_sr_blocks = 0;  // tune_nt: -1 auto
+    int last_np = 0;  // partial count written by the last ACC-carrying sweep
+    int res_cus = 0;  // compute units of the device
+    // operator and preconditioner
+    double shift = 0.0;  // the operator is A_poisson + shift I (gk_set_shift; a multigrid level's: 4^l times it)
+    int pkind = GK_PREC_IDENTITY, pdeg = 8;
+    double p0 = 8.2, p1 = 0.2;
+    int tune_cheb_fused = 1;  // temporal-blocked Chebyshev sweeps (single slab)
+    int tune_cheb_sten = 1;   // the Arnoldi step's pass forms z = A v itself (stage 0)
+    double *aux = nullptr, *dA = nullptr, *dB = nullptr;  // the Chebyshev sweeps' work vectors
+    double *red = nullptr;   // NSLOT * NPMAX partial slabs
+    double *scal = nullptr;  // 8 scalars
+};
+
+// One level of the GK_PREC_MG hierarchy (gk_op.hip: mg_build / mg_apply / mg_free).  g is a
+// bare grid -- the level's side, the parent's device and stream, set_geometry and the level's
+// Chebyshev smoother -- that the stencil and the sweeps run on; the vectors are carved from
+// the parent's mg_buf (level 0 smooths on the parent's aux, dA, dB).
 struct gk_mg_level {
-    gk_ctx *lc = nullptr;
+    gk_grid g;
     double *r = nullptr, *e = nullptr;                // level > 0: its input (restricted residual) and result
     double *z = nullptr, *t = nullptr, *d = nullptr;  // level < L: iterate, residual, post-smoothing correction
 };
 
-struct gk_ctx {
-    int dev = 0, N = 0, line0 = 0, nlines = 0, m = 0;
-    i64 nloc = 0, ld = 0, g0 = 0;
-    hipStream_t st = nullptr;
+struct gk_ctx : gk_grid {
+    int m = 0;
     // HBM residents
     double *V = nullptr;  // (m+1) columns, stride ld
-    double *w = nullptr, *z = nullptr, *aux = nullptr, *dA = nullptr, *dB = nullptr;
+    double *w = nullptr, *z = nullptr;
     double *x = nullptr, *b = nullptr, *vj = nullptr, *hlo = nullptr, *hhi = nullptr;
     double *dh = nullptr;  // deep halos of the Chebyshev pass inputs: [3 vectors][lo, hi][CF_HMAX lines][N]
     double *zline = nullptr;  // N zeros (the short-recurrence marches' line past a physical boundary)
-    double *red = nullptr;   // NSLOT * NPMAX partial slabs
     double *hcol = nullptr;  // m+2 Hessenberg column / scalars
     double *ydev = nullptr;  // m+1
     double *hb = nullptr;    // m+2 Householder broadcast buffer
-    double *scal = nullptr;  // 8 scalars
     double *hcol_host = nullptr;  // pinned
     double *hall = nullptr;       // device: per-step Hessenberg columns, m slots of m+2
     double *hallh = nullptr;      // mapped pinned host mirror of hall (written by k_scale)
@@ -73,9 +103,6 @@ struct gk_ctx {
     short2 *gram_pairs = nullptr;
     int gram_nblk = 0;
     // preconditioner
-    int pkind = GK_PREC_IDENTITY, pdeg = 8;
-    double p0 = 8.2, p1 = 0.2;
-    double shift = 0.0;        // the operator is A_poisson + shift I (gk_set_shift; a multigrid level's: 4^l times it)
     int side = GK_SIDE_LEFT;   // MGS-R: left (the reference) or right preconditioning (gk_set_precond_side)
     int tune_right_fused = 1;  // side right, cbpr2, one rank: w = A M^-1 v as one march (k_right_cbpr2)
     int basis = GK_BASIS_F64;  // MGS-R: storage precision of the Krylov columns (gk_set_basis_precision, gk_cb.hpp)
@@ -90,7 +117,7 @@ struct gk_ctx {
     int mg_deg = 0;                                // ... and the smoother degree (mg_refresh)
     int tune_mg_fused = 1;                         // GK_TUNE_MG_FUSED: residual and restriction in one march
     // decomposition / comm
-    int nranks = 1, rank = 0, max_lines = 0;
+    int nranks = 1, rank = 0;
     int min_lines = 0;  // smallest slab of any rank (0: not gathered yet; ensure_min_lines)
     ncclComm_t comm = nullptr;
     bool comm_ok = false;
@@ -119,7 +146,6 @@ struct gk_ctx {
     unsigned *hold_word = nullptr, *hold_word_dev = nullptr;  // gk_debug_hold_stream's mapped word
     int *res_err = nullptr, *res_err_dev = nullptr;  // mapped deadline flag
     unsigned res_tag = 1;                           // next granule tag (never 0)
-    int res_cus = 0;                                // compute units of the device
     int tune_res = -1;                              // -1 auto, 0 off, 1 on where possible
     int tune_res_r2 = 0;                            // cap of resident double2 per thread (0 = auto)
     int tune_res_pipe = -1;                         // w-only MGS step: pipelined pass (-1: the build's default)
@@ -136,18 +162,9 @@ struct gk_ctx {
     gk::u64 *res_trace = nullptr;                   // gk_profile_res_trace: [RGMAX][RES_TRACE_X][2] ticks
     int res_trace_j = 0, res_trace_mode = -1;       // the traced launch: step j, mode (-1 = off)
     int res_trace_g = 0, res_trace_np = 0;          // its workgroups and exchanges
-    // launch geometry
-    int vec = 2, JT = 16;
-    dim3 sgrid;
-    int sr_JT = 64, tune_sr_blocks = 0;  // the short-recurrence marches' geometry (gk_sr_*)
-    int tune_sr_two = 1;                 // GK_TUNE_SR_TWO_LEVEL
-    bool sr_two = false;                 // this solve runs the two-level marches (set by gk_sr_start)
-    dim3 sr_sgrid;
-    int np_sr = 0;
-    int np_st = 0, np_pj = 0, nblk_stream = 0;
-    int last_np = 0;          // partial count written by the last ACC-carrying sweep
-    int tune_cheb_fused = 1;  // temporal-blocked Chebyshev sweeps (single slab)
-    int tune_cheb_sten = 1;   // the Arnoldi step's pass forms z = A v itself (stage 0)
+    // tuning knobs (gk_set_tuning)
+    int tune_sr_two = 1;      // GK_TUNE_SR_TWO_LEVEL
+    bool sr_two = false;      // this solve runs the two-level marches (set by gk_sr_start)
     int tune_spin_wait = 1;   // the per-step host wait spins on its event (0: hipEventSynchronize)
     int tune_graph = 1;       // launch-path MGS-R steps captured as hipGraphs (RCCL / no collective)
     int tune_res_qdef = -1;   // k_mgs_res NT: V_q of the LDS / streamed parts with the default policy (-1 auto)
@@ -159,9 +176,6 @@ struct gk_ctx {
     unsigned graph_seq0 = 0;            // xs_seq when the capture in progress began
     unsigned *xs_seqdev = nullptr;      // device: the sequence base of a replayed graph's exchanges
     bool capturing = false;   // a step is being captured: no profiling events inside it
-    // tuning knobs (gk_set_tuning)
-    int tune_nt = -1, tune_pj_blocks = 0, tune_st_blocks = 0;  // tune_nt: -1 auto
-    bool nt_auto = false;
     int prof_every = 1;       // record events in steps with j % prof_every == 0
     bool prof_on_step = true;
     // state
@@ -218,7 +232,7 @@ constexpr int PROF_POOL = 8192;
 // gk_api.hip
 int prof_harvest(gk_ctx *c);
 void graph_reset(gk_ctx *c);
-void set_geometry(gk_ctx *c);
+void set_geometry(gk_grid *g);
 int check_ctx(gk_ctx *c);
 // ... and the range checks of the step and the update / v_err entries
 inline int check_step(const gk_ctx *c, int j) {
@@ -233,9 +247,9 @@ inline int check_nout(const gk_ctx *c, int n_out) {
 // running gk_sr_* solve -- later gk_sr_iterate / status / history refuse until the
 // next gk_sr_start.
 inline void sr_invalidate(gk_ctx *c) { c->sr_solver = -1; }
-// The diagonal of the context's operator A_poisson + shift I, the `diag` every stencil-carrying
+// The diagonal of the grid's operator A_poisson + shift I, the `diag` every stencil-carrying
 // kernel takes: fl(4 + shift), rounded once here and never in a kernel.
-inline double diag_of(const gk_ctx *c) { return 4.0 + c->shift; }
+inline double diag_of(const gk_grid *g) { return 4.0 + g->shift; }
 // The context's side: the MGS-R cycle's.  The short-recurrence solvers and Householder's
 // GK_HH_PREC_LEFT precondition on the left only; GK_HH_PREC_RIGHT does not ask the context.
 inline bool right_prec(const gk_ctx *c) { return c->side == GK_SIDE_RIGHT && c->pkind != GK_PREC_IDENTITY; }
@@ -250,7 +264,7 @@ inline T *vcol(const gk_ctx *c, int k) { return reinterpret_cast<T *>(c->V) + (i
 inline double *cb_v1w(const gk_ctx *c) { return c->V + (i64)(c->m - 1) * c->ld; }
 inline double *cb_vjw(const gk_ctx *c) { return c->V + (i64)c->m * c->ld; }
 // The Krylov columns by non-temporal loads (GK_TUNE_PROJ_NT; auto: set_geometry's nt_auto)
-inline bool nt_cols(const gk_ctx *c) { return c->tune_nt > 0 || (c->tune_nt < 0 && c->nt_auto); }
+inline bool nt_cols(const gk_grid *g) { return g->tune_nt > 0 || (g->tune_nt < 0 && g->nt_auto); }
 // H(1:j+1, j) of step j: its device slot, the mapped mirror the step's last kernel publishes
 // it to (the device's address of it) and the host's view of that mirror
 struct HCol { double *dev, *map; const volatile double *host; };
@@ -261,11 +275,14 @@ inline HCol hcol_of(const gk_ctx *c, int j) {
 
 // gk_op.hip -- the operator A, the preconditioner M and their products.  acc: the reduction
 // fused into the launch that writes `out` (gk::ACC_*; ACC_DOT with vdot), its partials in
-// `part`, their count in c->last_np.  Every one exchanges the halos of what it reads.
+// `part`, their count in last_np.  Every one exchanges the halos of what it reads.  What takes
+// a gk_grid * runs on a bare grid too; a multigrid preconditioner needs the context.
 int op_A(gk_ctx *c, const double *v, double *out, int acc, const double *vdot, double *part);
 int op_resid(gk_ctx *c, const double *x, double *out, int acc, double *part);  // out = b - A x
-int stencil_plain_raw(gk_ctx *c, const double *x, const double *hlo, const double *hhi, double *y);
+int stencil_plain_raw(gk_grid *g, const double *x, const double *hlo, const double *hhi, double *y);
+int grid_sweeps(gk_grid *g, const double *in, double *out, int acc, const double *vdot, double *part);
 int precond_sweeps(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part);
+int grid_Minv_or_copy(gk_grid *g, const double *in, double *out);
 int op_Minv_or_copy(gk_ctx *c, const double *in, double *out);
 int op_precond(gk_ctx *c, const double *v, double *out, bool resid, int acc, const double *vdot, double *part);
 int op_right(gk_ctx *c, const double *v, double *out, int acc, const double *vdot, double *part);
@@ -281,13 +298,13 @@ int mg_transfer(gk_ctx *c, int what, int level, const double *a, const double *b
 
 // gk_step.hip -- what every Arnoldi path launches, and the MGS-R cycle.  proj: one k_proj
 // launch on double columns (mode: gk::PJ_*; the float-column form stays inside the unit).
-int proj(gk_ctx *c, int mode, double *w, const double *va, const double *vb, const double *pin, int npin,
+int proj(gk_grid *g, int mode, double *w, const double *va, const double *vb, const double *pin, int npin,
          double *pout, double *hslot, double coef, i64 tail0 = 0, int hstore = 0);
 int scale(gk_ctx *c, double *out, const double *w, const double *pin, int npin, double *hslot,
           double *hcopy = nullptr, const double *hsrc = nullptr, int ncopy = 0, bool pin_norm = false);
 int add_into(gk_ctx *c, double *x, const double *w);  // x += w (k_add, GK_KID_UPDATE)
 int fill_hash(gk_ctx *c, double *x, unsigned long long seed);  // k_fill_hash of the global index
-int finalize(gk_ctx *c, const double *pin, int npin, double *out, int take_sqrt);
+int finalize(gk_grid *g, const double *pin, int npin, double *out, int take_sqrt);
 bool res_plan(gk_ctx *c, gk::ResPlan &p, bool hh = false);
 enum { RESF_CLOSE_HH = 1, RESF_UNIT_INIT = 2, RESF_PIN_LOCAL = 4 };  // res_step's flags
 int res_step(gk_ctx *c, int j, const gk::ResPlan &p, const double *pin, int npin, double *hs, double *hcopy,
@@ -300,7 +317,7 @@ int gram(gk_ctx *c, const double *base, int ncols, std::vector<double> &G);
 int update_begin(gk_ctx *c, const double *y, int n_out);  // gk_update_x / gk_hh_update_x: checks, y to ydev
 
 // gk_comm.hip
-bool collective(const gk_ctx *c);
+bool collective(const gk_grid *g);  // false on a bare grid
 void xs_set_timeout(gk_ctx *c, int ms);
 int xs_check(gk_ctx *c);
 int res_check(gk_ctx *c);
@@ -315,16 +332,16 @@ inline int sync_harvest(gk_ctx *c) {
 }
 int allreduce(gk_ctx *c, double *buf, int count, bool vec = false);
 int bcast(gk_ctx *c, double *buf, int count, int root);
-int halo_lines(gk_ctx *c, const double *vec, int nl, double *lo, double *hi);
-int halo(gk_ctx *c, const double *vec);
-const double *halo_lo(gk_ctx *c);
-const double *halo_hi(gk_ctx *c);
+int halo_lines(gk_grid *g, const double *vec, int nl, double *lo, double *hi);
+int halo(gk_grid *g, const double *vec);
+const double *halo_lo(const gk_grid *g);
+const double *halo_hi(const gk_grid *g);
 
 struct ProfScope {
     gk_ctx *c;
     int slot = -1;
-    ProfScope(gk_ctx *c_, int kid) : c(c_) {
-        if (!c->prof || !c->prof_on_step || c->capturing) return;
+    ProfScope(gk_grid *g, int kid) : c(g->ctx) {
+        if (c == nullptr || !c->prof || !c->prof_on_step || c->capturing) return;
         if (c->nev == PROF_POOL) prof_harvest(c);
         slot = c->nev++;
         c->evk[slot] = kid;
@@ -335,6 +352,6 @@ struct ProfScope {
     }
 };
 
-inline double *slot(gk_ctx *c, int s) { return c->red + (i64)s * gk::NPMAX; }
+inline double *slot(const gk_grid *g, int s) { return g->red + (i64)s * gk::NPMAX; }
 
 }  // namespace gkh

@@ -16,26 +16,26 @@ namespace gkh __attribute__((visibility("hidden"))) {
 
 // -------------------------------------------------------------- launches ---
 template <int VEC, int OP, int ACC>
-int launch_stencil_v(gk_ctx *c, const gk::StArgs &a) {
+int launch_stencil_v(gk_grid *c, const gk::StArgs &a) {
     gk::k_stencil<VEC, OP, ACC><<<c->sgrid, gk::TPB, 0, c->st>>>(a);
     LAUNCHCHK();
     return GK_OK;
 }
 
 template <int OP, int ACC>
-int launch_stencil_o(gk_ctx *c, const gk::StArgs &a) {
+int launch_stencil_o(gk_grid *c, const gk::StArgs &a) {
     return c->vec == 2 ? launch_stencil_v<2, OP, ACC>(c, a) : launch_stencil_v<1, OP, ACC>(c, a);
 }
 
 template <int OP>
-int launch_stencil_a(gk_ctx *c, int acc, const gk::StArgs &a) {
+int launch_stencil_a(gk_grid *c, int acc, const gk::StArgs &a) {
     if (acc == gk::ACC_NONE) return launch_stencil_o<OP, gk::ACC_NONE>(c, a);
     if (acc == gk::ACC_DOT) return launch_stencil_o<OP, gk::ACC_DOT>(c, a);
     return launch_stencil_o<OP, gk::ACC_NORM>(c, a);
 }
 
-// One sweep on the context's slab, its halo lines already exchanged (halo(c, a.x)).
-int stencil(gk_ctx *c, int op, int acc, gk::StArgs a) {
+// One sweep on the grid's slab, its halo lines already exchanged (halo(c, a.x)).
+int stencil(gk_grid *c, int op, int acc, gk::StArgs a) {
     ProfScope ps(c, GK_KID_STENCIL);
     if (acc != gk::ACC_NONE) c->last_np = c->np_st;
     a.hlo = halo_lo(c);
@@ -81,8 +81,8 @@ int op_resid(gk_ctx *c, const double *x, double *out, int acc, double *part) {
 }
 
 // y = A x on a slab whose neighbour lines the caller holds (nullptr: physical boundary):
-// no communicator, no profiling scope -- gk_poisson5's stack context.
-int stencil_plain_raw(gk_ctx *c, const double *x, const double *hlo, const double *hhi, double *y) {
+// no communicator, no profiling scope -- gk_poisson5's bare grid.
+int stencil_plain_raw(gk_grid *c, const double *x, const double *hlo, const double *hhi, double *y) {
     gk::StArgs a{};
     a.x = x;
     a.y = y;
@@ -96,7 +96,7 @@ int stencil_plain_raw(gk_ctx *c, const double *x, const double *hlo, const doubl
 }
 
 // cbpr2 coefficients exactly as chebyshev.f90:19-25
-void cbpr2_coefs(const gk_ctx *c, double *d_out, double *alpha_out) {
+void cbpr2_coefs(const gk_grid *c, double *d_out, double *alpha_out) {
     const double em = c->p0, eM = c->p1;
     const double cc = (eM - em) / 2.0;
     const double d = (eM + em) / 2.0;
@@ -149,14 +149,14 @@ int right_cbpr2(gk_ctx *c, const double *v, double *out, int acc, const double *
 // One temporal-blocked pass (gk_cheb.hip), tiles sized by the largest slab so
 // every rank writes the same number of partials (the all-reduced slab has one
 // length on all ranks).
-int launch_cf(gk_ctx *c, int L, bool first, bool last, int acc, gk::CFArgs &a, i64 *np, bool sten = false) {
+int launch_cf(gk_grid *c, int L, bool first, bool last, int acc, gk::CFArgs &a, i64 *np, bool sten = false) {
     gk::CFLaunch q{};
     q.L = L;
     q.sten = sten;
     q.first = first;
     q.last = last;
     q.acc = acc;
-    q.lines = (c->nranks > 1 && c->max_lines > c->nlines) ? c->max_lines : c->nlines;
+    q.lines = (c->ctx != nullptr && c->ctx->nranks > 1 && c->max_lines > c->nlines) ? c->max_lines : c->nlines;
     q.cus = c->res_cus > 0 ? c->res_cus : 256;
     q.dev = c->dev;
     q.st = c->st;
@@ -172,17 +172,18 @@ int launch_cf(gk_ctx *c, int L, bool first, bool last, int acc, gk::CFArgs &a, i
 // Chebyshev(k <= 16) as one or two temporal-blocked passes (gk_cheb.hip):
 // sweeps 1..min(k, 8) in the first, the rest in the second.  The input is `in`, or
 // with sten_v the vector whose stencil image stage 0 forms.
-int cheb_fused(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part,
+int cheb_fused(gk_grid *c, const double *in, double *out, int acc, const double *vdot, double *part,
                const double *c1, const double *c2, double theta, const double *sten_v) {
     ProfScope ps(c, GK_KID_PREC);
     const int k = c->pdeg;
     const int g1 = std::min(k, gk::CF_LMAX), g2 = k - g1;
     const bool sten = sten_v != nullptr;  // one pass (k <= 8) taking v, stage 0 = the stencil
     // On slabs every input of a pass brings L lines of each neighbour (deep halo).
-    const bool slabs = collective(c) && c->nranks > 1;
-    const bool has_lo = slabs && c->rank > 0, has_hi = slabs && c->rank < c->nranks - 1;
-    auto dlo = [&](int v) { return c->dh + (i64)(2 * v) * gk::CF_HMAX * c->N; };
-    auto dhi = [&](int v) { return c->dh + (i64)(2 * v + 1) * gk::CF_HMAX * c->N; };
+    const gk_ctx *cx = c->ctx;  // the slabs' context (a bare grid is never one of several)
+    const bool slabs = collective(c) && cx->nranks > 1;
+    const bool has_lo = slabs && cx->rank > 0, has_hi = slabs && cx->rank < cx->nranks - 1;
+    auto dlo = [&](int v) { return cx->dh + (i64)(2 * v) * gk::CF_HMAX * c->N; };
+    auto dhi = [&](int v) { return cx->dh + (i64)(2 * v + 1) * gk::CF_HMAX * c->N; };
     auto deep = [&](gk::CFArgs &x, int v, const double *vec, int L) -> int {
         if (slabs) CHK(halo_lines(c, vec, L, dlo(v), dhi(v)));
         x.lo[v] = has_lo ? dlo(v) : nullptr;
@@ -243,10 +244,6 @@ int cheb_fused(gk_ctx *c, const double *in, double *out, int acc, const double *
 // slab_partition's.
 int ensure_min_lines(gk_ctx *c) {
     if (c->min_lines > 0) return GK_OK;
-    if (!collective(c) || c->nranks == 1) {
-        c->min_lines = c->nlines;
-        return GK_OK;
-    }
     std::vector<double> v(c->nranks, 0.0);
     v[c->rank] = c->nlines;
     double *d = slot(c, 3);
@@ -264,23 +261,23 @@ int ensure_min_lines(gk_ctx *c) {
 // slabs below 2 GiB per vector, and on slabs every rank holding at least the
 // pass's L lines (the deep halo comes from the immediate neighbour only).  The
 // same answer on every rank.
-int cheb_fused_ok(gk_ctx *c, bool *ok) {
+int cheb_fused_ok(gk_grid *c, bool *ok) {
     *ok = false;
     if (!c->tune_cheb_fused || c->N % 2 != 0 || c->pdeg > 2 * gk::CF_LMAX) return GK_OK;
     // the pass addresses slab vectors through 32-bit buffer offsets
     if ((i64)c->N * std::max(c->nlines, c->max_lines) * 8 >= (1LL << 31)) return GK_OK;
-    if (!collective(c) || c->nranks == 1) {
+    if (!collective(c) || c->ctx->nranks == 1) {
         *ok = true;
         return GK_OK;
     }
-    CHK(ensure_min_lines(c));
-    *ok = c->min_lines >= std::min(c->pdeg, gk::CF_LMAX);
+    CHK(ensure_min_lines(c->ctx));
+    *ok = c->ctx->min_lines >= std::min(c->pdeg, gk::CF_LMAX);
     return GK_OK;
 }
 
 // Chebyshev(k) coefficients of the sweeps (the per-sweep kernels' recurrence), k each.
 constexpr int CHEB_KMAX = 64;  // gk_set_precond's bound on the degree
-void cheb_coefs(const gk_ctx *c, double *c1, double *c2, double *theta) {
+void cheb_coefs(const gk_grid *c, double *c1, double *c2, double *theta) {
     *theta = (c->p0 + c->p1) / 2.0;
     const double delta = std::fabs(c->p1 - c->p0) / 2.0;
     const double sigma = *theta / delta;
@@ -296,11 +293,10 @@ void cheb_coefs(const gk_ctx *c, double *c1, double *c2, double *theta) {
 // ------------------------------------------------ multigrid (GK_PREC_MG) ---
 // Aggregation multigrid on 2 x 2 blocks: with piecewise-constant P and the 4-member sum
 // P^T, P^T A_N P = 2 A_{N/2} -- every level runs the unscaled stencil on a smaller square
-// grid, so a level is a light context (its side, set_geometry, a Chebyshev smoother) that
-// stencil() and precond_sweeps() run on unchanged, and the cycle is a composition of them
+// grid, so a level is a bare gk_grid (its side, set_geometry, a Chebyshev smoother) that
+// stencil() and grid_sweeps() run on unchanged, and the cycle is a composition of them
 // with gk_mg.hpp's three streaming launches.
 void mg_free(gk_ctx *c) {
-    for (gk_mg_level &lv : c->mg) delete lv.lc;
     c->mg.clear();
     if (c->mg_buf != nullptr) {  // queued cycles may still read it
         if (c->st != nullptr) (void)hipStreamSynchronize(c->st);
@@ -343,20 +339,19 @@ int mg_build(gk_ctx *c, double p0, double p1, int degree) {
     for (int l = 0; l <= L; ++l) {
         gk_mg_level &lv = c->mg[l];
         const int n = sides[l];
-        gk_ctx *lc = new gk_ctx();
-        lv.lc = lc;
-        lc->dev = c->dev;
-        lc->N = n;
-        lc->nlines = n;
-        lc->max_lines = n;
-        lc->nloc = (i64)n * n;
-        lc->ld = vlen(n);
-        lc->st = c->st;
-        lc->red = c->red;
-        lc->scal = c->scal;
-        lc->res_cus = c->res_cus;
-        set_geometry(lc);
-        lc->pkind = GK_PREC_CHEB;
+        gk_grid *gr = &lv.g;  // its block-count tunings stay at their defaults, whatever the parent's
+        gr->dev = c->dev;
+        gr->N = n;
+        gr->nlines = n;
+        gr->max_lines = n;
+        gr->nloc = (i64)n * n;
+        gr->ld = vlen(n);
+        gr->st = c->st;
+        gr->red = c->red;
+        gr->scal = c->scal;
+        gr->res_cus = c->res_cus;
+        set_geometry(gr);
+        gr->pkind = GK_PREC_CHEB;
         if (l > 0) {
             lv.r = take(n);
             lv.e = take(n);
@@ -367,13 +362,13 @@ int mg_build(gk_ctx *c, double p0, double p1, int degree) {
             lv.d = take(n);
         }
         if (l == 0) {
-            lc->aux = c->aux;
-            lc->dA = c->dA;
-            lc->dB = c->dB;
+            gr->aux = c->aux;
+            gr->dA = c->dA;
+            gr->dB = c->dB;
         } else {
-            lc->aux = take(n);
-            lc->dA = take(n);
-            lc->dB = take(n);
+            gr->aux = take(n);
+            gr->dA = take(n);
+            gr->dB = take(n);
         }
     }
     mg_refresh(c);
@@ -392,37 +387,37 @@ void mg_refresh(gk_ctx *c) {
     const int L = (int)c->mg.size() - 1;
     double sl = c->shift;
     for (int l = 0; l <= L; ++l, sl *= 4.0) {
-        gk_ctx *lc = c->mg[l].lc;
-        lc->shift = sl;
+        gk_grid *gr = &c->mg[l].g;
+        gr->shift = sl;
         if (l < L) {
-            lc->p0 = c->mg_p0 + (sl - c->shift);
-            lc->p1 = c->mg_p1 + (sl - c->shift);
-            lc->pdeg = c->mg_deg;
+            gr->p0 = c->mg_p0 + (sl - c->shift);
+            gr->p1 = c->mg_p1 + (sl - c->shift);
+            gr->pdeg = c->mg_deg;
         } else {
-            c->mg_cdeg = gk::mg_coarse_degree(lc->N, sl, &lc->p0, &lc->p1);
-            lc->pdeg = c->mg_cdeg;
+            c->mg_cdeg = gk::mg_coarse_degree(gr->N, sl, &gr->p0, &gr->p1);
+            gr->pdeg = c->mg_cdeg;
         }
     }
 }
 
-// out = r - A z on level context lc (OP_RESID's expression with in1 = r)
-static int mg_resid(gk_ctx *lc, const double *z, const double *r, double *out) {
+// out = r - A z on level grid gr (OP_RESID's expression with in1 = r)
+static int mg_resid(gk_grid *gr, const double *z, const double *r, double *out) {
     gk::StArgs a{};
     a.x = z;
     a.in1 = r;
     a.y = out;
-    return stencil(lc, gk::OP_RESID, gk::ACC_NONE, a);
+    return stencil(gr, gk::OP_RESID, gk::ACC_NONE, a);
 }
 
 // rc = P^T (r - A z): one march (GK_TUNE_MG_FUSED), or OP_RESID into t and the plain
 // restriction -- the same expressions in the same order, bit-identical rc.
 static int mg_resid_restrict(gk_ctx *c, gk_mg_level &lv, const double *r, double *rc) {
     if (c->tune_mg_fused) {
-        HIPCHK(gk::mg_restrict(true, lv.lc->N, diag_of(lv.lc), lv.z, r, rc, c->st));
+        HIPCHK(gk::mg_restrict(true, lv.g.N, diag_of(&lv.g), lv.z, r, rc, c->st));
         return GK_OK;
     }
-    CHK(mg_resid(lv.lc, lv.z, r, lv.t));
-    HIPCHK(gk::mg_restrict(false, lv.lc->N, 0.0, lv.t, nullptr, rc, c->st));
+    CHK(mg_resid(&lv.g, lv.z, r, lv.t));
+    HIPCHK(gk::mg_restrict(false, lv.g.N, 0.0, lv.t, nullptr, rc, c->st));
     return GK_OK;
 }
 
@@ -434,28 +429,25 @@ int mg_apply(gk_ctx *c, const double *in, double *out, int acc, const double *vd
     if (c->mg.size() < 2) return set_err(GK_ERR_STATE, "multigrid hierarchy not built");
     ProfScope ps(c, GK_KID_PREC);
     const int L = (int)c->mg.size() - 1;
-    for (gk_mg_level &lv : c->mg) {  // the smoothers follow the parent's Chebyshev route
-        lv.lc->tune_cheb_fused = c->tune_cheb_fused;
-        lv.lc->st = c->st;
-    }
+    for (gk_mg_level &lv : c->mg) lv.g.tune_cheb_fused = c->tune_cheb_fused;  // the smoothers follow the parent's route
     for (int l = 0; l < L; ++l) {  // pre-smoothing from zero, residual, restriction
         gk_mg_level &lv = c->mg[l];
         const double *r = l == 0 ? in : lv.r;
-        CHK(precond_sweeps(lv.lc, r, lv.z, gk::ACC_NONE, nullptr, nullptr));
+        CHK(grid_sweeps(&lv.g, r, lv.z, gk::ACC_NONE, nullptr, nullptr));
         CHK(mg_resid_restrict(c, lv, r, c->mg[l + 1].r));
     }
-    CHK(precond_sweeps(c->mg[L].lc, c->mg[L].r, c->mg[L].e, gk::ACC_NONE, nullptr, nullptr));
+    CHK(grid_sweeps(&c->mg[L].g, c->mg[L].r, c->mg[L].e, gk::ACC_NONE, nullptr, nullptr));
     for (int l = L - 1; l >= 0; --l) {  // correction, post-smoothing on the new residual
         gk_mg_level &lv = c->mg[l];
-        gk_ctx *lc = lv.lc;
+        gk_grid *gr = &lv.g;
         const double *r = l == 0 ? in : lv.r;
-        HIPCHK(gk::mg_prolong_add(lc->N, lv.z, c->mg[l + 1].e, lv.z, c->st));
-        CHK(mg_resid(lc, lv.z, r, lv.t));
-        CHK(precond_sweeps(lc, lv.t, lv.d, gk::ACC_NONE, nullptr, nullptr));
-        HIPCHK(gk::mg_add(l == 0 ? acc : gk::ACC_NONE, lc->nblk_stream, lc->nloc, lv.z, lv.d, l == 0 ? out : lv.e,
+        HIPCHK(gk::mg_prolong_add(gr->N, lv.z, c->mg[l + 1].e, lv.z, c->st));
+        CHK(mg_resid(gr, lv.z, r, lv.t));
+        CHK(grid_sweeps(gr, lv.t, lv.d, gk::ACC_NONE, nullptr, nullptr));
+        HIPCHK(gk::mg_add(l == 0 ? acc : gk::ACC_NONE, gr->nblk_stream, gr->nloc, lv.z, lv.d, l == 0 ? out : lv.e,
                           vdot, part, c->st));
     }
-    if (acc != gk::ACC_NONE) c->last_np = c->mg[0].lc->nblk_stream;
+    if (acc != gk::ACC_NONE) c->last_np = c->mg[0].g.nblk_stream;
     return GK_OK;
 }
 
@@ -463,8 +455,8 @@ int mg_apply(gk_ctx *c, const double *in, double *out, int acc, const double *vd
 // the hierarchy's own vectors.
 int mg_transfer(gk_ctx *c, int what, int level, const double *a, const double *b, double *out) {
     gk_mg_level &f = c->mg[level], &g = c->mg[level + 1];
-    const int N = f.lc->N;
-    const size_t nf = sizeof(double) * (size_t)f.lc->nloc, nc = sizeof(double) * (size_t)g.lc->nloc;
+    const int N = f.g.N;
+    const size_t nf = sizeof(double) * (size_t)f.g.nloc, nc = sizeof(double) * (size_t)g.g.nloc;
     if (what == 2) {  // out = a + P b, in place as the cycle runs it
         HIPCHK(hipMemcpyAsync(f.z, a, nf, hipMemcpyHostToDevice, c->st));
         HIPCHK(hipMemcpyAsync(g.e, b, nc, hipMemcpyHostToDevice, c->st));
@@ -475,7 +467,7 @@ int mg_transfer(gk_ctx *c, int what, int level, const double *a, const double *b
     HIPCHK(hipMemcpyAsync(f.t, a, nf, hipMemcpyHostToDevice, c->st));
     if (what == 1) {  // out = P^T (a - A b) by the fused march
         HIPCHK(hipMemcpyAsync(f.z, b, nf, hipMemcpyHostToDevice, c->st));
-        HIPCHK(gk::mg_restrict(true, N, diag_of(f.lc), f.z, f.t, g.r, c->st));
+        HIPCHK(gk::mg_restrict(true, N, diag_of(&f.g), f.z, f.t, g.r, c->st));
     } else {  // out = P^T a
         HIPCHK(gk::mg_restrict(false, N, 0.0, f.t, nullptr, g.r, c->st));
     }
@@ -483,11 +475,9 @@ int mg_transfer(gk_ctx *c, int what, int level, const double *a, const double *b
     return sync_st(c);
 }
 
-// out = M^-1 in (cbpr2, Chebyshev sweeps or the multigrid cycle); `in` is read in place
-// (in != out, and for Chebyshev and multigrid neither is one of the sweeps' work vectors
-// aux, dA, dB).
-int precond_sweeps(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part) {
-    if (c->pkind == GK_PREC_MG) return mg_apply(c, in, out, acc, vdot, part);
+// out = M^-1 in by cbpr2 or the Chebyshev sweeps; `in` is read in place (in != out, and for
+// Chebyshev neither is one of the sweeps' work vectors aux, dA, dB).
+int grid_sweeps(gk_grid *c, const double *in, double *out, int acc, const double *vdot, double *part) {
     bool fused = false;
     if (c->pkind == GK_PREC_CHEB) CHK(cheb_fused_ok(c, &fused));
     if (!fused) CHK(halo(c, in));  // the fused passes bring their own deep halos
@@ -537,11 +527,19 @@ int precond_sweeps(gk_ctx *c, const double *in, double *out, int acc, const doub
     return GK_OK;
 }
 
+// ... or the multigrid cycle, which is the context's (the same rule for its vectors)
+int precond_sweeps(gk_ctx *c, const double *in, double *out, int acc, const double *vdot, double *part) {
+    return c->pkind == GK_PREC_MG ? mg_apply(c, in, out, acc, vdot, part) : grid_sweeps(c, in, out, acc, vdot, part);
+}
+
 // out = M^-1 in where M may be the identity (then a device copy)
-int op_Minv_or_copy(gk_ctx *c, const double *in, double *out) {
-    if (c->pkind != GK_PREC_IDENTITY) return precond_sweeps(c, in, out, gk::ACC_NONE, nullptr, nullptr);
+int grid_Minv_or_copy(gk_grid *c, const double *in, double *out) {
+    if (c->pkind != GK_PREC_IDENTITY) return grid_sweeps(c, in, out, gk::ACC_NONE, nullptr, nullptr);
     HIPCHK(hipMemcpyAsync(out, in, sizeof(double) * c->nloc, hipMemcpyDeviceToDevice, c->st));
     return GK_OK;
+}
+int op_Minv_or_copy(gk_ctx *c, const double *in, double *out) {
+    return c->pkind == GK_PREC_MG ? mg_apply(c, in, out, gk::ACC_NONE, nullptr, nullptr) : grid_Minv_or_copy(c, in, out);
 }
 
 // The Arnoldi step's out = M^-1 (A v) with Chebyshev(k <= 8) as ONE pass whose

@@ -23,7 +23,7 @@ namespace gkh __attribute__((visibility("hidden"))) {
 // -------------------------------------------------------------- launches ---
 // T: the type va / vb are stored in (float: the FP32 basis, PJ_AXPY_DOT / PJ_AXPY_NORM only)
 template <bool NT, int U, class T>
-void launch_proj_u(gk_ctx *c, int mode, double *w, const T *va, const T *vb, const double *pin, int npin,
+void launch_proj_u(gk_grid *c, int mode, double *w, const T *va, const T *vb, const double *pin, int npin,
                    double *pout, double *hslot, double coef, i64 tail0, int hstore) {
     const dim3 g(c->np_pj);
     const i64 n = c->nloc;
@@ -48,7 +48,7 @@ void launch_proj_u(gk_ctx *c, int mode, double *w, const T *va, const T *vb, con
 }
 
 template <bool NT, class T>
-void launch_proj(gk_ctx *c, int mode, double *w, const T *va, const T *vb, const double *pin, int npin,
+void launch_proj(gk_grid *c, int mode, double *w, const T *va, const T *vb, const double *pin, int npin,
                  double *pout, double *hslot, double coef, i64 tail0, int hstore) {
     // loads in flight per thread and array: one trip per thread when the vector is small, else 2
     const i64 per_thread = (c->nloc / 2 + (i64)c->np_pj * gk::TPB - 1) / ((i64)c->np_pj * gk::TPB);
@@ -60,7 +60,7 @@ void launch_proj(gk_ctx *c, int mode, double *w, const T *va, const T *vb, const
 
 // (T is named, never deduced: callers pass nullptr for the column a mode does not read)
 template <class T>
-int proj_t(gk_ctx *c, int mode, double *w, const std::common_type_t<T> *va, const std::common_type_t<T> *vb,
+int proj_t(gk_grid *c, int mode, double *w, const std::common_type_t<T> *va, const std::common_type_t<T> *vb,
            const double *pin, int npin, double *pout, double *hslot, double coef, i64 tail0 = 0, int hstore = 0) {
     if (!std::is_same<T, double>::value && mode != gk::PJ_AXPY_DOT && mode != gk::PJ_AXPY_NORM)
         return set_err(GK_ERR_STATE, "projection mode %d on float columns", mode);
@@ -73,7 +73,7 @@ int proj_t(gk_ctx *c, int mode, double *w, const std::common_type_t<T> *va, cons
     return GK_OK;
 }
 
-int proj(gk_ctx *c, int mode, double *w, const double *va, const double *vb, const double *pin, int npin,
+int proj(gk_grid *c, int mode, double *w, const double *va, const double *vb, const double *pin, int npin,
          double *pout, double *hslot, double coef, i64 tail0, int hstore) {
     return proj_t<double>(c, mode, w, va, vb, pin, npin, pout, hslot, coef, tail0, hstore);
 }
@@ -125,7 +125,7 @@ int fill_hash(gk_ctx *c, double *x, unsigned long long seed) {
     return GK_OK;
 }
 
-int finalize(gk_ctx *c, const double *pin, int npin, double *out, int take_sqrt) {
+int finalize(gk_grid *c, const double *pin, int npin, double *out, int take_sqrt) {
     ProfScope ps(c, GK_KID_OTHER);
     gk::k_finalize<<<1, gk::TPB, 0, c->st>>>(pin, npin, out, take_sqrt);
     LAUNCHCHK();

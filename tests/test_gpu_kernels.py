@@ -78,6 +78,52 @@ def test_precond_bitexact(oracle, N, kind, degree):
     assert np.array_equal(zd.cpu().numpy(), ref)
 
 
+def test_precond_apply_refusals(oracle):
+    """What gk_precond_apply refuses, each with GK_ERR_ARG and before any launch; then the
+    identity without params copies r, and a valid cbpr2 call after all the refusals is
+    bit-equal to the oracle (nothing of a refused call stays behind)."""
+    import ctypes
+
+    from gmres_amd import _native as nat
+
+    N = 16
+    r = np.random.default_rng(5).standard_normal(N * N)
+    rd = _dev(r)
+    zd = torch.zeros_like(rd)
+    scratch = torch.zeros(3 * N * N, dtype=torch.float64, device="cuda")
+    pad = torch.zeros(N * N + 1, dtype=torch.float64, device="cuda")  # pad[1:] sits 8 bytes off
+    assert pad.data_ptr() % 16 == 0
+
+    def apply(kind, params, degree, rp=None, zp=None, sp=scratch.data_ptr()):
+        pp = (ctypes.c_double * 2)(*params) if params is not None else None
+        return nat.hip().gk_precond_apply(N, kind, pp, degree, rp or rd.data_ptr(), zp or zd.data_ptr(), sp, None)
+
+    iv = (8.2, 0.2)
+    refused = {
+        "Chebyshev without scratch": apply(nat.GK_PREC_CHEB, iv, 4, sp=None),
+        "Chebyshev degree 0": apply(nat.GK_PREC_CHEB, iv, 0),
+        "Chebyshev degree 65": apply(nat.GK_PREC_CHEB, iv, 65),
+        "kind above the enum": apply(7, iv, 1),
+        "kind below the enum": apply(-1, iv, 1),
+        "multigrid": apply(nat.GK_PREC_MG, iv, 2),
+        "cbpr2 without params": apply(nat.GK_PREC_CBPR2, None, 1),
+        "Chebyshev on an empty interval": apply(nat.GK_PREC_CHEB, (3.0, 3.0), 4),
+        "r 8 bytes off": apply(nat.GK_PREC_CBPR2, iv, 1, rp=pad.data_ptr() + 8),
+        "z 8 bytes off": apply(nat.GK_PREC_CBPR2, iv, 1, zp=pad.data_ptr() + 8),
+        "scratch 8 bytes off": apply(nat.GK_PREC_CBPR2, iv, 1, sp=scratch.data_ptr() + 8),
+    }
+    assert refused == {what: nat.GK_ERR_ARG for what in refused}
+    torch.cuda.synchronize()
+    assert not zd.any().item()  # no refused call wrote z
+
+    assert apply(nat.GK_PREC_IDENTITY, None, 1) == nat.GK_OK
+    torch.cuda.synchronize()
+    assert np.array_equal(zd.cpu().numpy(), r)
+    assert apply(nat.GK_PREC_CBPR2, iv, 1) == nat.GK_OK
+    torch.cuda.synchronize()
+    assert np.array_equal(zd.cpu().numpy(), oracle.precond(oracle.PREC_CBPR2, r, N, params=iv, degree=1))
+
+
 @pytest.mark.parametrize("N", [2, 65, 514])
 @pytest.mark.parametrize("kind,degree", [("identity", 1), ("cbpr2", 1), ("cheb", 4)])
 def test_context_apply_bitexact(oracle, N, kind, degree):

@@ -121,6 +121,21 @@ def test_line_march_is_stated_once():
     assert fused == ["gk_cheb.hip"], fused
 
 
+def test_only_gk_create_builds_a_context():
+    """A gk_ctx exists only as gk_create built it: no other unit allocates one or declares one by
+    value.  What runs on less -- a multigrid level, a stateless call -- takes a gk_grid, so the
+    compiler holds it to the members a bare grid has."""
+    csrc = os.path.join(ROOT, "gmres_amd", "csrc")
+    by_value = re.compile(r"\bgk_ctx\s+[A-Za-z_]\w*\s*[;={]")
+    news, values = [], []
+    for f in sorted(os.listdir(csrc)):
+        txt = open(os.path.join(csrc, f)).read()
+        news += [f] * len(re.findall(r"\bnew\s+gk_ctx\b", txt))
+        values += [f"{f}: {m.group(0)}" for m in by_value.finditer(txt)]
+    assert news == ["gk_api.hip"], news
+    assert values == [], values
+
+
 def test_build_refuses_chebyshev_scratch_spills():
     """gmres_amd/build.py parses the resource-usage remarks of the Chebyshev
     translation units and fails the build when any k_cheb_fused instantiation
